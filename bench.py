@@ -11,14 +11,28 @@ per-module clip, Adam) on one batch of synthetic rays already resident in HBM
 owns `batch_size` rays (weak scaling), one RCCL all-reduce of the flat fp32 gradient
 per step.  Rank 0 prints ONE JSON line.
 
-roofline: the dominant kernels are the bf16 MFMA kernels (gemm_nt_kernel forward/dX,
+A plain run does only what the headline needs: set up, `--warmup` steps, `--steps` timed steps, the result line
+(`value` = rays/s over the timed steps, `ms_per_step` = wall-clock milliseconds of one timed step).  `--full` adds
+everything else, as before: per-step HIP-event times, the roofline (an instrumented pass of its own), `aux` (other shapes
+and presets, the render path) and `cpu_baseline`; `--no_aux` / `--no_cpu_baseline` drop parts of it.
+
+Every step (warm-up, timed, instrumented) starts from the same parameters, the seeded initial weights; the Adam moments and
+step count carry on.  The rays and the jitter are seeded too, so the same arguments give the last timed step the same inputs
+on every run.
+
+--dump-outputs DIR: after the timed steps, what the last one handed its caller (the new parameters and Adam moments, the
+step's statistics) as DIR/<name>.npy, float32 / float64, < 64 MB in all; the moments as a fixed seeded sample of their
+elements.  Two runs agree up to the order of the weight-gradient atomics (~1e-7 relative), so two builds can be compared
+output for output.
+
+roofline (--full): the dominant kernels are the bf16 MFMA kernels (gemm_nt_kernel forward/dX,
 gemm_tn_kernel dW, the fused per-level chain kernels of the proposal MLP).  achieved = algorithmic training FLOPs of one step (SURVEY.md 8d:
 1815.994 MFLOP/ray at 360.gin x rays per launch-set) / summed duration of those
 kernels within the step, measured with HIP events on the launch stream during the
 timed region (a second, identical, instrumented pass so the events do not perturb
 `value`).  peak = 2500 TFLOP/s dense bf16 (MI355X_MICROARCH.md).
 
-cpu_baseline: the torch-CPU oracle ("port" of the reference's jax-cpu path: JAX is not
+cpu_baseline (--full): the torch-CPU oracle ("port" of the reference's jax-cpu path: JAX is not
 installable here) running the same train_step on a bounded sample, host cores stated.
 """
 
@@ -76,125 +90,49 @@ def algorithmic_flops_per_ray(model):
   return fwd, train
 
 
-def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--gpus', type=int, default=1)
-  ap.add_argument('--steps', type=int, default=20)
-  ap.add_argument('--warmup', type=int, default=5)
-  ap.add_argument('--batch_size', type=int, default=16384, help='rays per GPU (Config.batch_size of 360.gin)')
-  ap.add_argument('--global_batch', type=int, default=0,
-                  help='total rays per step over all GPUs (overrides --batch_size: rays per GPU = global_batch / gpus, "strong" '
-                       'scaling); BASELINE config 3 is --gpus 8 --global_batch 65536')
-  ap.add_argument('--preset', default='360')
-  ap.add_argument('--gin_bindings', action='append', default=[])
-  ap.add_argument('--no_cpu_baseline', action='store_true')
-  ap.add_argument('--cpu_rays', type=int, default=256, help='rays of the CPU-baseline sample (SURVEY 8d: B = 256)')
-  ap.add_argument('--check_collectives', action='store_true',
-                  help='before the benchmark: all-reduce / all-gather known patterns over the process group, assert the results '
-                       'and time a 36 MB fp32 all-reduce (first contact with RCCL must not be the first bug)')
-  ap.add_argument('--no_aux', action='store_true', help='skip the secondary measurements (4096x192 north-star shape, render)')
-  ap.add_argument('--pair_dxdw', type=int, default=-1, help='A/B: models._PAIR_DXDW (1 on, 0 off; default: the module\'s own setting)')
-  ap.add_argument('--tangent_chain', type=int, default=-1, help='A/B: models._TANGENT_CHAIN (1 on, 0 off; default: the module\'s own setting)')
-  ap.add_argument('--head_k32', type=int, default=-1, help='A/B: models._HEAD_K32')
-  ap.add_argument('--rank1_last', type=int, default=-1, help='A/B: models._RANK1_LAST (1 on, 0 off; default: the module\'s own setting)')
-  args = ap.parse_args()
+DUMP_PARAMS_MAX = 10_000_000      # parameters written whole up to this count (9,007,493 at 360.gin: 36 MB of float32)
+DUMP_MOMENTS_SAMPLE = 1 << 20     # elements of each Adam moment: a fixed seeded sample (4 MB each)
+DUMP_MAX_BYTES = 64 << 20
 
-  # torch-only preflight in a child process before this process creates a HIP context (multinerf_amd/preflight.py): a box
-  # whose first host -> device copy aborts is then on record as `BOX_FAULT: ...` instead of a core dump of the benchmark
-  pre = None
-  # (on EVERY local rank: the HSA_ENABLE_SDMA=0 workaround lives in the environment of the process that found it needed)
-  if os.environ.get('MNR_SKIP_PREFLIGHT') != '1':
-    from multinerf_amd import preflight
-    pre = preflight.check(verbose=False)
-    if not pre['ok']:
-      raise SystemExit('BOX_FAULT: torch-only preflight failed (lines above); libmnerf_hip.so was never loaded')
 
-  from multinerf_amd import configs, dist as mdist, models, ops, synthetic, train_utils
-  from multinerf_amd import streams as mstreams
+def dump_outputs(path, state, stats):
+  """--dump-outputs: what train_pstep returned to its caller in the last timed step, as <path>/<name>.npy."""
 
-  if args.pair_dxdw >= 0:
-    models._PAIR_DXDW = bool(args.pair_dxdw)
-  if args.rank1_last >= 0:
-    models._RANK1_LAST = bool(args.rank1_last)
-  if args.head_k32 >= 0:
-    models._HEAD_K32 = bool(args.head_k32)
-  if args.tangent_chain >= 0:
-    models._TANGENT_CHAIN = bool(args.tangent_chain)
-  mdist.init_from_env()
-  rank, world = mdist.rank(), mdist.world_size()
-  if world != args.gpus:
-    raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE is {world}: launch with torch.distributed.run')
-  local = int(os.environ.get('LOCAL_RANK', '0'))
-  ndev = torch.cuda.device_count()
-  if ndev < 1:
-    raise SystemExit('bench.py needs a GPU (the HIP path has no CPU fallback)')
-  if local >= ndev:
-    raise SystemExit(f'LOCAL_RANK {local} but only {ndev} visible GPU(s): one process per GPU on ONE node')
-  torch.cuda.set_device(local)
-  dev = torch.device('cuda', local)
-  dist_info = mdist.describe(dev)
-  if world > 1:
-    # every rank must sit on its own device: gather (hostname, device index, PCI bus id) and fail loudly on a clash
-    ids = mdist.all_gather_objects((os.uname().nodename, local, dist_info['device_uuid']))
-    if len(set(ids)) != world:
-      raise SystemExit(f'rank / device mismatch: {ids}')
-    dist_info['rank_devices'] = [list(i) for i in ids]
-  if args.check_collectives or (world > 1 and os.environ.get('MNR_SKIP_COLLECTIVE_CHECK') != '1'):
-    dist_info['collective_check'] = mdist.check_collectives(dev)
+  def sample(x, k, seed):
+    if x.numel() <= k:
+      return x
+    idx = np.sort(np.random.default_rng(seed).choice(x.numel(), k, replace=False))
+    return x[torch.as_tensor(idx, device=x.device)]
 
-  cfg = configs.load_preset(args.preset, args.gin_bindings)
-  if args.global_batch:
-    if args.global_batch % world:
-      raise SystemExit(f'--global_batch {args.global_batch} is not a multiple of --gpus {world}')
-    args.batch_size = args.global_batch // world
-  cfg.batch_size = args.batch_size
-  model, state, render_eval_pfn, train_pstep, lr_fn = train_utils.setup_model(cfg, 0, device=dev)
-  B = args.batch_size
-  batch = synthetic.synthetic_rays(B, seed=20200823 + rank, near=cfg.near, far=cfg.far).map(lambda t: t.to(dev))
-  gen = torch.Generator(device=dev).manual_seed(1234 + rank)
-  if cfg.compute_normal_metrics:      # blender ground-truth normals / alphas (synthetic)
-    batch.alphas = torch.rand((B,), generator=gen, device=dev)
-    batch.normals = torch.randn((B, 3), generator=gen, device=dev)
-  if cfg.compute_disp_metrics:
-    batch.disps = torch.rand((B,), generator=gen, device=dev)
-  if cfg.rawnerf_mode:                # RawNeRF: per-ray exposure index / value, Bayer-mask lossmult
-    batch.rays.exposure_idx = torch.randint(0, 5, (B, 1), generator=gen, device=dev).to(torch.int32)
-    batch.rays.exposure_values = 0.5 + torch.rand((B, 1), generator=gen, device=dev)
-    batch.rays.lossmult = (torch.rand((B, 3), generator=gen, device=dev) > 0.4).float()
-  train_frac = 0.5
+  s = stats.materialize()
+  arrays = {
+      'params': sample(state.params['flat'], DUMP_PARAMS_MAX, 0),
+      'adam_mu_sample': sample(state.mu, DUMP_MOMENTS_SAMPLE, 1),
+      'adam_nu_sample': sample(state.nu, DUMP_MOMENTS_SAMPLE, 2),
+      'stats_raw': stats['_raw'],                   # the step's statistics vector (losses, MSEs per level, ...)
+      'grad_norms': torch.as_tensor(s['grad_norms']),
+      'loss': torch.tensor([s['loss']], dtype=torch.float64),
+      'psnrs': torch.as_tensor(s['psnrs'], dtype=torch.float64),
+  }
+  arrays = {k: v.detach().cpu().numpy().reshape(-1) for k, v in arrays.items()}
+  arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+  total = sum(v.nbytes for v in arrays.values())
+  if total > DUMP_MAX_BYTES:
+    raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget')
+  os.makedirs(path, exist_ok=True)
+  for k, v in arrays.items():
+    np.save(os.path.join(path, f'{k}.npy'), v)
 
-  def step():
-    nonlocal state
-    state, stats, _ = train_pstep(gen, state, batch, None, train_frac, 0.0)
-    return stats
 
-  for _ in range(args.warmup):
-    stats = step()
-  torch.cuda.synchronize()
-  mdist.barrier()
-  torch.cuda.synchronize()
-  # per-step HIP events on the launch stream (median of per-step hipEvent times); `value` stays the wall clock
-  # over exactly K steps between the two barrier + synchronize brackets
-  evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-  t0 = time.perf_counter()
-  evs[0].record()
-  for i in range(args.steps):
-    stats = step()
-    evs[i + 1].record()
-  torch.cuda.synchronize()
-  mdist.barrier()
-  torch.cuda.synchronize()
-  elapsed = time.perf_counter() - t0
+def full_measurements(args, evs, model, state, step, render_eval_pfn, batch, gen, dev, world, rank, B, elapsed, train_frac,
+                      fwd_flops, train_flops, lib_info):
+  """--full: what the headline does not need.  Per-step HIP-event times of the timed steps (`evs`), the roofline of the
+  dominant kernels (an instrumented pass of its own), the secondary measurements of `aux`."""
+  from multinerf_amd import configs, dist as mdist, ops, synthetic, train_utils
   step_ms = sorted(evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps))
   median_ms = step_ms[len(step_ms) // 2] if len(step_ms) % 2 else 0.5 * (step_ms[len(step_ms) // 2 - 1] + step_ms[len(step_ms) // 2])
-  if world > 1:
-    t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-    torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-    elapsed = float(t.item())
-  s = stats.materialize()
 
   # ---- roofline of the dominant kernels: instrumented pass (HIP events around every GEMM launch)
-  fwd_flops, train_flops = algorithmic_flops_per_ray(model)
   ops.PROFILE.enable()
   nprof = max(1, min(3, args.steps))
   for _ in range(nprof):
@@ -282,8 +220,6 @@ def main():
   # same workload); null for any other workload.  tools/profile_round.sh regenerates the inputs.
   traffic, traffic_note = None, 'no PMC pass for this workload'
   tpath = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'profiles', 'traffic.json')
-  from multinerf_amd import _lib as mlib
-  lib_info = mlib.describe()
   if args.preset == '360' and not args.gin_bindings and B == 16384 and os.path.exists(tpath):
     with open(tpath) as f:
       tj = json.load(f)
@@ -292,6 +228,175 @@ def main():
     else:
       traffic_note = (f"profiles/traffic.json was measured on build {str(tj.get('lib_digest'))[:12]}, the loaded library is "
                       f"{str(lib_info.get('source_digest'))[:12]}: not reported")
+
+  ms_per_step = 1e3 * elapsed / args.steps
+  roofline = {
+    'bound': 'mfma',
+    'kernel': 'gemm_nt_kernel + gemm_nt_panel_kernel + gemm_nt_wres_kernel + gemm_tn_kernel + gemm_tn_gcol_kernel + gemm_tn_rank1_kernel + mlp_chain_fwd/bwd_kernel (bf16 MFMA 32x32x16)',
+    'achieved': achieved_tflops,
+    'peak': 2500.0,
+    'unit': 'TFLOP/s',
+    'frac': achieved_tflops / 2500.0,
+    # two fractions of the same 2.5 PFLOP/s: `frac` / `gemm_frac` = algorithmic FLOPs / time spent INSIDE the MFMA
+    # kernels (HIP events); `whole_step_frac` = SURVEY 8(d)'s definition, rays/s x FLOPs/ray / peak per GPU
+    'gemm_frac': achieved_tflops / 2500.0,
+    # With the proposal levels' backward on its own stream (multinerf_amd/streams.py, the default) MFMA kernels of
+    # two streams overlap: `gemm_ms_per_step` is the UNION of their launch intervals (time during which at least one
+    # MFMA kernel runs), `gemm_ms_per_step_sum_of_launches` the plain sum (what a rocprofv3 --stats table adds up
+    # to: a launch that shares the chip takes longer).  MNR_SIDE_STREAM=0 makes the two equal.
+    'frac_definition': 'algorithmic training FLOPs per step / union of the MFMA kernels\' launch intervals / 2.5 PFLOP/s',
+    'whole_step_achieved': train_flops * B / (ms_per_step * 1e-3) / 1e12,
+    'whole_step_frac': train_flops * B / (ms_per_step * 1e-3) / 2.5e15,
+    'traffic': traffic,
+    'traffic_source': traffic_note,
+    'gemm_ms_per_step': gemm_ms_per_step,
+    'gemm_ms_per_step_sum_of_launches': gemm_ms_sum / nprof,
+    'gemm_launches_per_step': gemm_launches / nprof,
+    'gemm_share_of_step': gemm_ms_per_step / ms_per_step,
+    'hbm_bound_kernels': hbm_kernels,
+  }
+  return {'ms_per_step_median_hip_event': median_ms, 'ms_per_step_min_max_hip_event': [step_ms[0], step_ms[-1]],
+          'roofline': roofline, 'aux': aux}
+
+
+def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--gpus', type=int, default=1)
+  ap.add_argument('--steps', type=int, default=20)
+  ap.add_argument('--warmup', type=int, default=5)
+  ap.add_argument('--batch_size', type=int, default=16384, help='rays per GPU (Config.batch_size of 360.gin)')
+  ap.add_argument('--global_batch', type=int, default=0,
+                  help='total rays per step over all GPUs (overrides --batch_size: rays per GPU = global_batch / gpus, "strong" '
+                       'scaling); BASELINE config 3 is --gpus 8 --global_batch 65536')
+  ap.add_argument('--preset', default='360')
+  ap.add_argument('--gin_bindings', action='append', default=[])
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what the headline does not need: per-step HIP events, roofline (instrumented pass), aux, '
+                       'cpu_baseline')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps, write what the last one returned (parameters, Adam moments, statistics) as DIR/*.npy')
+  ap.add_argument('--no_cpu_baseline', action='store_true')
+  ap.add_argument('--cpu_rays', type=int, default=256, help='rays of the CPU-baseline sample (SURVEY 8d: B = 256)')
+  ap.add_argument('--check_collectives', action='store_true',
+                  help='before the benchmark: all-reduce / all-gather known patterns over the process group, assert the results '
+                       'and time a 36 MB fp32 all-reduce (first contact with RCCL must not be the first bug)')
+  ap.add_argument('--no_aux', action='store_true', help='skip the secondary measurements (4096x192 north-star shape, render)')
+  ap.add_argument('--pair_dxdw', type=int, default=-1, help='A/B: models._PAIR_DXDW (1 on, 0 off; default: the module\'s own setting)')
+  ap.add_argument('--tangent_chain', type=int, default=-1, help='A/B: models._TANGENT_CHAIN (1 on, 0 off; default: the module\'s own setting)')
+  ap.add_argument('--head_k32', type=int, default=-1, help='A/B: models._HEAD_K32')
+  ap.add_argument('--rank1_last', type=int, default=-1, help='A/B: models._RANK1_LAST (1 on, 0 off; default: the module\'s own setting)')
+  args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be >= 1 and --warmup >= 0')
+
+  # torch-only preflight in a child process before this process creates a HIP context (multinerf_amd/preflight.py): a box
+  # whose first host -> device copy aborts is then on record as `BOX_FAULT: ...` instead of a core dump of the benchmark
+  pre = None
+  # (on EVERY local rank: the HSA_ENABLE_SDMA=0 workaround lives in the environment of the process that found it needed)
+  if os.environ.get('MNR_SKIP_PREFLIGHT') != '1':
+    from multinerf_amd import preflight
+    pre = preflight.check(verbose=False)
+    if not pre['ok']:
+      raise SystemExit('BOX_FAULT: torch-only preflight failed (lines above); libmnerf_hip.so was never loaded')
+
+  from multinerf_amd import configs, dist as mdist, models, synthetic, train_utils
+  from multinerf_amd import streams as mstreams
+
+  if args.pair_dxdw >= 0:
+    models._PAIR_DXDW = bool(args.pair_dxdw)
+  if args.rank1_last >= 0:
+    models._RANK1_LAST = bool(args.rank1_last)
+  if args.head_k32 >= 0:
+    models._HEAD_K32 = bool(args.head_k32)
+  if args.tangent_chain >= 0:
+    models._TANGENT_CHAIN = bool(args.tangent_chain)
+  mdist.init_from_env()
+  rank, world = mdist.rank(), mdist.world_size()
+  if world != args.gpus:
+    raise SystemExit(f'--gpus {args.gpus} but WORLD_SIZE is {world}: launch with torch.distributed.run')
+  local = int(os.environ.get('LOCAL_RANK', '0'))
+  ndev = torch.cuda.device_count()
+  if ndev < 1:
+    raise SystemExit('bench.py needs a GPU (the HIP path has no CPU fallback)')
+  if local >= ndev:
+    raise SystemExit(f'LOCAL_RANK {local} but only {ndev} visible GPU(s): one process per GPU on ONE node')
+  torch.cuda.set_device(local)
+  dev = torch.device('cuda', local)
+  dist_info = mdist.describe(dev)
+  if world > 1:
+    # every rank must sit on its own device: gather (hostname, device index, PCI bus id) and fail loudly on a clash
+    ids = mdist.all_gather_objects((os.uname().nodename, local, dist_info['device_uuid']))
+    if len(set(ids)) != world:
+      raise SystemExit(f'rank / device mismatch: {ids}')
+    dist_info['rank_devices'] = [list(i) for i in ids]
+  if args.check_collectives or (args.full and world > 1 and os.environ.get('MNR_SKIP_COLLECTIVE_CHECK') != '1'):
+    dist_info['collective_check'] = mdist.check_collectives(dev)
+
+  cfg = configs.load_preset(args.preset, args.gin_bindings)
+  if args.global_batch:
+    if args.global_batch % world:
+      raise SystemExit(f'--global_batch {args.global_batch} is not a multiple of --gpus {world}')
+    args.batch_size = args.global_batch // world
+  cfg.batch_size = args.batch_size
+  model, state, render_eval_pfn, train_pstep, lr_fn = train_utils.setup_model(cfg, 0, device=dev)
+  B = args.batch_size
+  batch = synthetic.synthetic_rays(B, seed=20200823 + rank, near=cfg.near, far=cfg.far).map(lambda t: t.to(dev))
+  gen = torch.Generator(device=dev).manual_seed(1234 + rank)
+  if cfg.compute_normal_metrics:      # blender ground-truth normals / alphas (synthetic)
+    batch.alphas = torch.rand((B,), generator=gen, device=dev)
+    batch.normals = torch.randn((B, 3), generator=gen, device=dev)
+  if cfg.compute_disp_metrics:
+    batch.disps = torch.rand((B,), generator=gen, device=dev)
+  if cfg.rawnerf_mode:                # RawNeRF: per-ray exposure index / value, Bayer-mask lossmult
+    batch.rays.exposure_idx = torch.randint(0, 5, (B, 1), generator=gen, device=dev).to(torch.int32)
+    batch.rays.exposure_values = 0.5 + torch.rand((B, 1), generator=gen, device=dev)
+    batch.rays.lossmult = (torch.rand((B, 3), generator=gen, device=dev) > 0.4).float()
+  train_frac = 0.5
+
+  # Every step starts from the same parameters (the optimiser updates them in place; its moments and step count carry on).
+  # A step from given inputs computes the same up to the order of the weight-gradient atomics; carried from step to step
+  # through the parameters, that rounding grows into differences far beyond rounding within ten steps of training, so the
+  # last step's outputs would differ from run to run.  The kernels run are the same either way.
+  flat0 = state.params['flat'].clone()
+
+  def step():
+    nonlocal state
+    state.params['flat'].copy_(flat0)
+    state, stats, _ = train_pstep(gen, state, batch, None, train_frac, 0.0)
+    return stats
+
+  for _ in range(args.warmup):
+    stats = step()
+  torch.cuda.synchronize()
+  mdist.barrier()
+  torch.cuda.synchronize()
+  # --full: per-step HIP events on the launch stream (median of per-step hipEvent times); `value` stays the wall
+  # clock over exactly K steps between the two barrier + synchronize brackets
+  evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
+  t0 = time.perf_counter()
+  if evs:
+    evs[0].record()
+  for i in range(args.steps):
+    stats = step()
+    if evs:
+      evs[i + 1].record()
+  torch.cuda.synchronize()
+  mdist.barrier()
+  torch.cuda.synchronize()
+  elapsed = time.perf_counter() - t0
+  if world > 1:
+    t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+    torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+    elapsed = float(t.item())
+  s = stats.materialize()
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, state, stats)
+  fwd_flops, train_flops = algorithmic_flops_per_ray(model)
+  from multinerf_amd import _lib as mlib
+  lib_info = mlib.describe()
+  if args.full:
+    full = full_measurements(args, evs, model, state, step, render_eval_pfn, batch, gen, dev, world, rank, B, elapsed,
+                             train_frac, fwd_flops, train_flops, lib_info)
 
   out = None
   if rank == 0:
@@ -305,13 +410,13 @@ def main():
         'steps': args.steps,
         'warmup': args.warmup,
         'ms_per_step': ms_per_step,
-        'ms_per_step_median_hip_event': median_ms,
-        'ms_per_step_min_max_hip_event': [step_ms[0], step_ms[-1]],
+        **({k: full[k] for k in ('ms_per_step_median_hip_event', 'ms_per_step_min_max_hip_event')} if args.full else {}),
         'higher_is_better': True,
         'scaling': 'strong' if args.global_batch else 'weak',
         'vs_baseline': None,
         'dtype': 'bf16 MFMA inputs / fp32 accumulate, fp32 everywhere else',
         'data': 'synthetic rays (SURVEY 8d, seed 20200823+rank), he_uniform random-init weights, random jitter',
+        'state': 'every step starts from the initial weights; Adam moments and step count carry on',
         'config': {
             'workload': f'configs/360.gin native levels (64,64,32), train_step, batch_size={B} rays per GPU'
                         if args.preset == '360' and not args.gin_bindings else
@@ -328,41 +433,17 @@ def main():
             'final_loss': s['loss'], 'final_psnr': s['psnr'],
             'reference_anchor': 'derived 182,555 rays/s aggregate on unknown hardware (BASELINE.md); not a published per-device number',
         },
-        'roofline': {
-            'bound': 'mfma',
-            'kernel': 'gemm_nt_kernel + gemm_nt_panel_kernel + gemm_nt_wres_kernel + gemm_tn_kernel + gemm_tn_gcol_kernel + gemm_tn_rank1_kernel + mlp_chain_fwd/bwd_kernel (bf16 MFMA 32x32x16)',
-            'achieved': achieved_tflops,
-            'peak': 2500.0,
-            'unit': 'TFLOP/s',
-            'frac': achieved_tflops / 2500.0,
-            # two fractions of the same 2.5 PFLOP/s: `frac` / `gemm_frac` = algorithmic FLOPs / time spent INSIDE the MFMA
-            # kernels (HIP events); `whole_step_frac` = SURVEY 8(d)'s definition, rays/s x FLOPs/ray / peak per GPU
-            'gemm_frac': achieved_tflops / 2500.0,
-            # With the proposal levels' backward on its own stream (multinerf_amd/streams.py, the default) MFMA kernels of
-            # two streams overlap: `gemm_ms_per_step` is the UNION of their launch intervals (time during which at least one
-            # MFMA kernel runs), `gemm_ms_per_step_sum_of_launches` the plain sum (what a rocprofv3 --stats table adds up
-            # to: a launch that shares the chip takes longer).  MNR_SIDE_STREAM=0 makes the two equal.
-            'frac_definition': 'algorithmic training FLOPs per step / union of the MFMA kernels\' launch intervals / 2.5 PFLOP/s',
-            'whole_step_achieved': train_flops * B / (ms_per_step * 1e-3) / 1e12,
-            'whole_step_frac': train_flops * B / (ms_per_step * 1e-3) / 2.5e15,
-            'traffic': traffic,
-            'traffic_source': traffic_note,
-            'gemm_ms_per_step': gemm_ms_per_step,
-            'gemm_ms_per_step_sum_of_launches': gemm_ms_sum / nprof,
-            'gemm_launches_per_step': gemm_launches / nprof,
-            'gemm_share_of_step': gemm_ms_per_step / ms_per_step,
-            'hbm_bound_kernels': hbm_kernels,
-        },
+        **({'roofline': full['roofline']} if args.full else {}),
     }
-    if aux:
-      out['aux'] = aux
+    if args.full and full['aux']:
+      out['aux'] = full['aux']
     out['library'] = lib_info
     out['preflight'] = None if pre is None else {'ok': pre['ok'], 'workaround': pre['workaround'], 'versions': pre['versions']}
     out['distributed'] = dist_info
 
   # ---- CPU baseline (rank 0, N=1 only): the oracle on a bounded sample of the same workload (SURVEY 8d protocol:
   # B = 256 rays, forward and train_step separately, 1 warm-up + 3 timed runs each, medians)
-  if rank == 0 and world == 1 and not args.no_cpu_baseline:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
     from oracle import bridge as obridge
     from oracle import models as omodels
     from oracle import train_utils as otrain

@@ -18,7 +18,7 @@ Pinning status:
     they are pinned against the reference's OWN internal/models.py and
     internal/train_utils.py executed in this container on small stand-ins for
     flax.linen / gin / jax.random with exact complex-step derivatives
-    (tests/golden/make_golden_models.py -> tests/golden/models.npz, held at
+    (tests/golden/make_golden_models.py -> tests/golden/models_*.npz, held at
     rtol 1e-9 in float64 by tests/test_oracle_models_golden.py), and by the
     published parameter counts.
   * PARITY UNPINNED: optax.adam (restated from its published algorithm) and

@@ -24,7 +24,8 @@ Sizes are shrunk (widths, samples per level, ray count) so that the vectors stay
 BASELINE configurations (ray shape, distance warp, contraction, basis, dilation, annealing, single_mlp, opaque
 background, GLO, Ref-NeRF heads, RawNeRF exposure) is the config file's own.
 
-Run (build container only):  python tests/golden/make_golden_models.py   ->  tests/golden/models.npz
+Run (build container only):  python tests/golden/make_golden_models.py   ->  tests/golden/models_<k>.npz
+(split by case into files of at most SHARD_BYTES each; `load_gold()` reads them back as one mapping)
 """
 
 import functools
@@ -42,7 +43,9 @@ sys.path.insert(0, HERE)
 import make_golden  # noqa: E402  (the jax.numpy stand-in of the leaf goldens)
 
 REF = make_golden.REF
-OUT = os.path.join(HERE, 'models.npz')
+OUT = os.path.join(HERE, 'models.npz')      # (--out=<path>: one file, for a partial run with --only=<case>)
+SHARD_STEM = os.path.join(HERE, 'models_')
+SHARD_BYTES = 640 * 1024                     # raw bytes per shard: every committed file stays under 1 MiB (float64 barely compresses)
 
 # name -> (preset, gin overrides, rays, randomized, train_frac)
 CASES = {
@@ -700,14 +703,56 @@ def main():
                    'contract': rcoord.contract, 'train_utils': rtrain}
   g = {}
   only = [a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--only=')]
-  out = ([a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--out=')] or [OUT])[0]
+  out = [a.split('=', 1)[1] for a in sys.argv[1:] if a.startswith('--out=')]
   for case in CASES:
     if only and case not in only:
       continue
     g.update(run_case(case, rmodels, ref_callables, rnd_state, Key))
     print(case, 'ok')
-  np.savez_compressed(out, **g)
-  print(f'wrote {out}: {len(g)} arrays, {os.path.getsize(out)} bytes')
+  if out:
+    np.savez_compressed(out[0], **g)
+    print(f'wrote {out[0]}: {len(g)} arrays, {os.path.getsize(out[0])} bytes')
+  else:
+    save_shards(g)
+
+
+def save_shards(g):
+  """tests/golden/models_<k>.npz: whole cases (key prefix up to the first '/') packed in order, SHARD_BYTES raw bytes at most."""
+  import glob
+  for old in glob.glob(SHARD_STEM + '*.npz'):
+    os.remove(old)
+  shards, cur, size = [], {}, 0
+  for case in dict.fromkeys(k.split('/', 1)[0] for k in g):
+    arrs = {k: v for k, v in g.items() if k.split('/', 1)[0] == case}
+    n = sum(np.asarray(v).nbytes for v in arrs.values())
+    if cur and size + n > SHARD_BYTES:
+      shards.append(cur)
+      cur, size = {}, 0
+    cur.update(arrs)
+    size += n
+  if cur:
+    shards.append(cur)
+  for i, sh in enumerate(shards):
+    path = f'{SHARD_STEM}{i}.npz'
+    np.savez_compressed(path, **sh)
+    print(f'wrote {path}: {len(sh)} arrays, {os.path.getsize(path)} bytes')
+
+
+class Gold(dict):
+  """The shards as one mapping with np.load's `.files`."""
+
+  @property
+  def files(self):
+    return list(self)
+
+
+def load_gold():
+  import glob
+  gold = Gold()
+  for path in sorted(glob.glob(SHARD_STEM + '*.npz')):
+    with np.load(path) as z:
+      gold.update({k: z[k] for k in z.files})
+  return gold
 
 
 if __name__ == '__main__':

@@ -14,6 +14,16 @@ from multinerf_amd.synthetic import synthetic_rays, procedural_scene_rays  # noq
 from oracle.bridge import oracle_hparams, make_noise  # noqa: F401,E402
 
 
+def reference_gin_bindings(name):
+  """What the reference's configs/<name>.gin binds, {configurable: {parameter: value}} as gin._BINDINGS holds it after
+  parsing the file (recorded by tests/golden/make_golden_gin.py)."""
+  import json
+  import os
+  with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_gin_bindings.json')) as f:
+    rec = json.load(f)[name]
+  return {t: {a: gin._parse_value(v) for a, v in b.items()} for t, b in rec.items()}
+
+
 def assert_adam_matches_oracle(model, cfg, flat0, raw_grad, opt0, state2, what=''):
   """The optimiser arithmetic, numerically (train_utils.py:326-330 + optax.adam): the oracle's clip_gradients ->
   nan_to_num -> adam_update applied to the KERNEL's own raw gradient `raw_grad`, from parameters `flat0` and

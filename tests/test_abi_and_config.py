@@ -116,21 +116,19 @@ def test_gin_include_and_bindings(tmp_path):
   gin.clear_config()
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/configs'), reason='reference not mounted')
 @pytest.mark.parametrize('name', ['360', 'blender_256', 'blender_refnerf', 'llff_raw'])
 def test_presets_equal_reference_gin_files(name):
-  """The shipped presets bind exactly what the reference's .gin files bind."""
-  gin.clear_config()
-  gin.parse_config_file(f'/root/reference/configs/{name}.gin')
-  import copy
-  ref = copy.deepcopy(gin._BINDINGS)
+  """The shipped presets bind exactly what the reference's .gin files bind (recorded in
+  tests/golden/reference_gin_bindings.json)."""
+  from tests import helpers
+  ref = helpers.reference_gin_bindings(name)
   configs.load_preset(name)
   assert gin._BINDINGS == ref
   gin.clear_config()
 
 
 def test_every_ref_nerf_feature_set_of_the_goldens_has_a_hip_path():
-  """The sets of Ref-NeRF flags tests/golden/models.npz holds the reference's outputs for (make_golden_models.py CASES) are all
+  """The sets of Ref-NeRF flags tests/golden/models_*.npz hold the reference's outputs for (make_golden_models.py CASES) are all
   accepted by Model.hip_supported(); what the reference itself cannot run is named as such (models.py:434-435,560-563,
   ref_utils.py:147,154)."""
   import importlib.util

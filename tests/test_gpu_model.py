@@ -158,7 +158,7 @@ CASES = [
                          'NerfMLP.enable_pred_roughness = False', 'NerfMLP.use_diffuse_color = False', 'NerfMLP.use_specular_tint = False',
                          'NerfMLP.use_n_dot_v = False'], 12),
     # the Ref-NeRF head with one part switched off each (mnr_ref_head_fwd's feature bits; the reference's own outputs for these
-    # sets are in tests/golden/models.npz): reflections about the density gradient's normals (no predicted normals) ...
+    # sets are in tests/golden/models_*.npz): reflections about the density gradient's normals (no predicted normals) ...
     ('blender_refnerf', ['NerfMLP.enable_pred_normals = False', "Config.orientation_loss_target = 'normals'",
                          'Config.predicted_normal_loss_mult = 0.0', 'Config.predicted_normal_coarse_loss_mult = 0.0'], 8),
     # ... no n.v column; the positional encoding of the reflection direction instead of the IDE (roughness an output only);

@@ -48,10 +48,10 @@ def test_train_then_eval(tmp_path):
 
 
 def test_bench_json_contract():
-  """bench.py prints ONE JSON line with the driver's keys (+ roofline); cpu_baseline / aux legs are skipped here."""
+  """bench.py --full prints ONE JSON line with the driver's keys (+ roofline); cpu_baseline / aux legs are skipped here."""
   if not torch.cuda.is_available():
     pytest.skip('no GPU')
-  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--no_cpu_baseline',
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full', '--no_cpu_baseline',
                       '--no_aux'], capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT))
   assert r.returncode == 0, r.stderr[-2000:]
   lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -67,3 +67,40 @@ def test_bench_json_contract():
   assert rf['bound'] == 'mfma' and rf['unit'] == 'TFLOP/s' and abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-9
   assert 0.05 < rf['frac'] < 1.0 and d['value'] > 1e5
   assert abs(d['value'] - 16384 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-6
+
+
+def _plain_bench(out_dir):
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '6', '--warmup', '2',
+                      '--dump-outputs', str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT,
+                     env=dict(os.environ, PYTHONPATH=ROOT))
+  assert r.returncode == 0, r.stderr[-2000:]
+  lines = [l for l in r.stdout.splitlines() if l.strip()]
+  assert len(lines) == 1
+  return json.loads(lines[0])
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+  """A plain bench.py run: the headline keys, no --full measurements, `--steps` timed steps; --dump-outputs writes the last
+  timed step's results (float32 / float64 .npy, < 64 MB), the parameters whole at 360.gin.  A second run with the same
+  arguments writes the same outputs up to the order of the weight-gradient atomics (one step's rounding: ~1e-7 measured)."""
+  import numpy as np
+  if not torch.cuda.is_available():
+    pytest.skip('no GPU')
+  out_dir = tmp_path / 'outputs'
+  d = _plain_bench(out_dir)
+  assert d['metric'] == 'train_rays_per_sec' and d['unit'] == 'rays/s' and d['higher_is_better'] is True
+  assert d['dtype'] == 'bf16 MFMA inputs / fp32 accumulate, fp32 everywhere else'
+  assert d['steps'] == 6 and abs(d['value'] - 16384 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-6
+  assert not {'roofline', 'aux', 'cpu_baseline', 'ms_per_step_median_hip_event'} & set(d)
+  files = {f: np.load(out_dir / f) for f in os.listdir(out_dir)}
+  assert set(files) == {f'{k}.npy' for k in ('params', 'adam_mu_sample', 'adam_nu_sample', 'stats_raw', 'grad_norms', 'loss', 'psnrs')}
+  assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in files.values())
+  assert sum(a.nbytes for a in files.values()) <= 64 << 20
+  assert files['params.npy'].shape == (d['config']['params'],)
+  assert abs(float(files['loss.npy'][0]) - d['config']['final_loss']) <= 1e-6 * abs(d['config']['final_loss'])
+  _plain_bench(tmp_path / 'again')
+  for f, a in files.items():
+    b = np.load(tmp_path / 'again' / f)
+    assert b.shape == a.shape and b.dtype == a.dtype, f
+    diff = float(np.abs(a.astype(np.float64) - b.astype(np.float64)).max())
+    assert diff <= 1e-5 * float(np.abs(a).max()) + 1e-12, (f, diff)

@@ -43,14 +43,11 @@ def test_param_counts_match_published(name):
 
 @pytest.mark.parametrize('fname', list(PUBLISHED_FILES))
 def test_param_counts_of_the_other_reference_configs(fname):
-  """Read from the reference's own gin files when they are at hand (build container), else skipped."""
-  import os
-  path = os.path.join(os.environ.get('MULTINERF_REFERENCE', '/root/reference'), 'configs', fname)
-  if not os.path.exists(path):
-    pytest.skip('reference configs not present')
+  """Bound as the reference's own gin files bind (recorded in tests/golden/reference_gin_bindings.json)."""
   from multinerf_amd import gin
   gin.clear_config()
-  cfg = configs.load_config([path], [])
+  gin._BINDINGS.update(helpers.reference_gin_bindings(fname[:-len('.gin')]))
+  cfg = configs.load_config([], [])
   m = models.Model(config=cfg)
   om, on, op = helpers.oracle_hparams(m)
   assert omodels.param_count(omodels.init_params(om, on, op)) == PUBLISHED_FILES[fname]

@@ -1,4 +1,4 @@
-"""The oracle's Model / MLP composition against the reference's OWN models.py (tests/golden/models.npz).
+"""The oracle's Model / MLP composition against the reference's OWN models.py (tests/golden/models_*.npz).
 
 tests/golden/make_golden_models.py executes reference internal/models.py (imported from where it lies, nothing copied)
 on a NumPy float64 stand-in for jax.numpy with ~100 lines standing in for flax.linen / gin / jax.random, exact
@@ -31,7 +31,7 @@ CASES = _gen.CASES
 # tests/golden/make_golden_models.py `linearize`), whose 1e-12 error the sixteen IPE degrees' attenuation exp(-4^l var / 2)
 # amplifies: measured 6e-9 relative in raw_grad_density, held to 5e-8.  Everything else is exact to rounding and held to 1e-9.
 NESTED_FD = ('refnerf_contract',)
-GOLD = np.load(os.path.join(HERE, 'golden', 'models.npz'))
+GOLD = _gen.load_gold()
 
 
 def _sub(prefix):

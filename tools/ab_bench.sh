@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of bench.py under different environment switches:
 #   bash tools/ab_bench.sh <tag> "name1:VAR=1 VAR2=x" "name2:" ...      (writes gpurun_out/<tag>_ab.jsonl + a summary)
-# Every arm is the default `bench.py --no_cpu_baseline --no_aux` line (20 timed steps after 5 warm-up); arms run back to
+# Every arm is the default `bench.py --full --no_cpu_baseline --no_aux` line (20 timed steps after 5 warm-up); arms run back to
 # back on one box, which is the only comparison DESIGN.md quotes (box-to-box spread is +-3 %).
 set -u
 TAG=$1; shift
@@ -13,7 +13,7 @@ EXTRA=${AB_BENCH_ARGS:-}
 for arm in "$@"; do
   name=${arm%%:*}
   envs=${arm#*:}
-  line=$(cd $R && env $envs timeout 600 python bench.py --no_cpu_baseline --no_aux $EXTRA 2> $OUT/${TAG}_ab_${name}.err | tail -1)
+  line=$(cd $R && env $envs timeout 600 python bench.py --full --no_cpu_baseline --no_aux $EXTRA 2> $OUT/${TAG}_ab_${name}.err | tail -1)
   echo "{\"arm\": \"$name\", \"env\": \"$envs\", \"line\": ${line:-null}}" >> $OUT/${TAG}_ab.jsonl
 done
 python - "$OUT/${TAG}_ab.jsonl" <<'PY'

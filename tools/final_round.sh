@@ -12,7 +12,7 @@ bash tools/profile_round.sh $TAG
 export TMPDIR=/tmp
 export MNR_SKIP_PREFLIGHT=1   # (rocprofv3 follows the preflight child, and its --stats database then holds that process only)
 cd /tmp
-MNR_SIDE_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_serial_prof -- python $R/bench.py --steps 5 --warmup 2 --no_cpu_baseline --no_aux > $OUT/${TAG}_serial_prof.log 2>&1
-python $R/tools/prof_summary.py stats $OUT/${TAG}_serial_prof --title "rocprofv3 --kernel-trace --stats ($TAG, one stream)" --command "MNR_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no_cpu_baseline --no_aux" > $OUT/${TAG}_serial_kernel_stats.md
+MNR_SIDE_STREAM=0 timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_serial_prof -- python $R/bench.py --steps 5 --warmup 2 --full --no_cpu_baseline --no_aux > $OUT/${TAG}_serial_prof.log 2>&1
+python $R/tools/prof_summary.py stats $OUT/${TAG}_serial_prof --title "rocprofv3 --kernel-trace --stats ($TAG, one stream)" --command "MNR_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --full --no_cpu_baseline --no_aux" > $OUT/${TAG}_serial_kernel_stats.md
 rm -rf $OUT/${TAG}_serial_prof
 head -14 $OUT/${TAG}_serial_kernel_stats.md

@@ -13,7 +13,7 @@ if [ -n "$PROBE" ]; then
 fi
 for arm in other product other product; do
   if [ $arm = other ]; then export MNR_LIB_PATH=$OTHER; else unset MNR_LIB_PATH; fi
-  timeout 300 python bench.py --no_cpu_baseline --no_aux 2>/dev/null | tail -1 | python -c "
+  timeout 300 python bench.py --full --no_cpu_baseline --no_aux 2>/dev/null | tail -1 | python -c "
 import json,sys
 b=json.loads(sys.stdin.read()); print('$arm', round(b['value']), 'rays/s', round(b['ms_per_step'],3), 'ms  mfma union', round(b['roofline']['gemm_ms_per_step'],2), 'final_loss', round(b['config']['final_loss'],7), b['library']['path'])"
 done > gpurun_out/${TAG}_bench.txt 2>&1

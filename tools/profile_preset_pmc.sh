@@ -11,8 +11,8 @@ mkdir -p $OUT
 export TMPDIR=/tmp MNR_SKIP_PREFLIGHT=1
 cd /tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/${TAG}_pmc_$C -- python $R/bench.py "$@" --steps 2 --warmup 1 --no_cpu_baseline --no_aux > $OUT/${TAG}_pmc_$C.log 2>&1
-  python $R/tools/prof_summary.py pmc $OUT/${TAG}_pmc_$C --title "rocprofv3 --pmc $C ($TAG)" --command "rocprofv3 --kernel-trace --pmc $C -- python bench.py $* --steps 2 --warmup 1 --no_cpu_baseline --no_aux" --top 40 > $OUT/${TAG}_pmc_$C.md
+  timeout 400 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/${TAG}_pmc_$C -- python $R/bench.py "$@" --steps 2 --warmup 1 --full --no_cpu_baseline --no_aux > $OUT/${TAG}_pmc_$C.log 2>&1
+  python $R/tools/prof_summary.py pmc $OUT/${TAG}_pmc_$C --title "rocprofv3 --pmc $C ($TAG)" --command "rocprofv3 --kernel-trace --pmc $C -- python bench.py $* --steps 2 --warmup 1 --full --no_cpu_baseline --no_aux" --top 40 > $OUT/${TAG}_pmc_$C.md
   rm -rf $OUT/${TAG}_pmc_$C
 done
 python - "$OUT/${TAG}_pmc_FETCH_SIZE.md" "$OUT/${TAG}_pmc_WRITE_SIZE.md" "$OUT/${TAG}_bench.json" <<'PY' | tee $OUT/${TAG}_traffic.txt

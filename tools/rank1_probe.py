@@ -78,7 +78,7 @@ assert rel < 1e-3
 del model, flat, batch, gs
 torch.cuda.empty_cache()
 for arm in (0, 1, 0, 1):
-  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--no_cpu_baseline', '--no_aux', '--rank1_last', str(arm)],
+  r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--full', '--no_cpu_baseline', '--no_aux', '--rank1_last', str(arm)],
                      capture_output=True, text=True, env=dict(os.environ, MNR_SKIP_PREFLIGHT='1'))
   try:
     b = json.loads(r.stdout.strip().splitlines()[-1])

@@ -10,8 +10,8 @@ export MNR_SKIP_PREFLIGHT=1      # (rocprofv3 follows the preflight child, and i
 cd /tmp
 for arm in "" serial; do
   if [ -z "$arm" ]; then E=""; N=${TAG}; T="$TAG"; else E="MNR_SIDE_STREAM=0"; N=${TAG}_serial; T="$TAG, one stream"; fi
-  env $E timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${N}_prof -- python $R/bench.py --steps 10 --warmup 2 --no_cpu_baseline --no_aux > $OUT/${N}_prof.log 2>&1
-  python $R/tools/prof_summary.py stats $OUT/${N}_prof --title "rocprofv3 --kernel-trace --stats ($T)" --command "$E rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no_cpu_baseline --no_aux" > $OUT/${N}_kernel_stats.md
+  env $E timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/${N}_prof -- python $R/bench.py --steps 10 --warmup 2 --full --no_cpu_baseline --no_aux > $OUT/${N}_prof.log 2>&1
+  python $R/tools/prof_summary.py stats $OUT/${N}_prof --title "rocprofv3 --kernel-trace --stats ($T)" --command "$E rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --full --no_cpu_baseline --no_aux" > $OUT/${N}_kernel_stats.md
   rm -rf $OUT/${N}_prof
   head -16 $OUT/${N}_kernel_stats.md | cut -c1-160
 done
