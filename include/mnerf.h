@@ -605,6 +605,38 @@ int mnr_lossfun_outer(int64_t B, int n, const float* t, const float* w, int ne, 
                       const float* w_env, float* out, void* stream);
 int mnr_lossfun_distortion(int64_t B, int n, const float* t, const float* w, float* out, void* stream);
 
+/* RobustNeRF (Config.data_loss_type = 'robustnerf'): the binary inlier mask of robustnerf.py:23-86 for one level's
+ * rendering.  The first B_valid rays are num_patches * P * P pixels in [patch][y][x] order, one workgroup per patch.
+ * A pixel is kept when its error mean_c (rgb - gt)^2 lies below *loss_threshold, or when more than
+ * 1 - smoothed_inlier_quantile of its f x f neighbourhood does ('SAME' zero padding, always over f * f), or when it lies
+ * in the centred inner x inner square of a patch of which more than 1 - inner_patch_inlier_quantile of the pixels pass
+ * one of the first two tests.  Votes are counted in integers and compared as count / n in double.  enable = 0: the
+ * mask is all ones (robustnerf.py:29-33) and only stats[3] is produced.  Limits: P * P <= 1024, f odd and <= P,
+ * inner <= P, B_valid a multiple of P * P.  Nothing is read back: the threshold and the results stay on the device. */
+typedef struct {
+  int64_t B, B_valid;              /* rays (padded), rays that take part */
+  int patch_size, inner_patch_size, filter_size, enable;
+  double smoothed_inlier_quantile, inner_patch_inlier_quantile;
+  const float* rgb;                /* [B,3] rendered */
+  const float* gt;                 /* [B,3] */
+  const float* lossmult;           /* [B,lm_c] */
+  int lm_c;                        /* 1 or 3 */
+  const float* loss_threshold;     /* device scalar */
+  const float* denom;              /* device scalar (mnr_lossmult_sum); read only when mse is given */
+  float* mask;                     /* [B]: 1 inlier, 0 outlier, 0 for the padding rays */
+  float* lossmult_out;             /* [B,lm_c] = lossmult * mask, may be NULL */
+  float* err;                      /* [B]: per-pixel error mean_c (rgb - gt)^2 of the first B_valid rays (mnr_quantile's input), may be NULL */
+  float* stats;                    /* [4] += mean is_inlier_loss, has_inlier_neighbors, is_inlier_patch, mask; may be NULL */
+  float* mse;                      /* [1] += sum(lossmult * (rgb - gt)^2) / *denom with the UNMASKED lossmult
+                                      (train_utils.py:86-88); may be NULL */
+} mnr_robust_args;
+int mnr_robustnerf_mask(const mnr_robust_args* args, void* stream);
+
+/* jnp.quantile(x[0:N], q), linear interpolation between the two exact order statistics at floor and ceil of
+ * q * (M - 1) over the M finite values of x (non-finite values are ignored; *out = NaN when there is none).  Exact
+ * selection (radix select on the bit patterns) in one workgroup, deterministic, any N >= 1, 0 <= q <= 1. */
+int mnr_quantile(int64_t N, const float* x, double q, float* out, void* stream);
+
 /* ------------------------------------------------------------------------- *
  * Optimiser  (replaces train_utils.clip_gradients train_utils.py:200-218,
  * jnp.nan_to_num :328 and optax.adam state.apply_gradients :330,372)

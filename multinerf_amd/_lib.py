@@ -147,6 +147,14 @@ class IdeTables(C.Structure):
   _fields_ = [('T', C.c_int), ('lmax', C.c_int), ('m', vp), ('l', vp), ('sigma', vp), ('mat', vp)]
 
 
+class RobustArgs(C.Structure):
+  _fields_ = [('B', C.c_int64), ('B_valid', C.c_int64),
+              ('patch_size', C.c_int), ('inner_patch_size', C.c_int), ('filter_size', C.c_int), ('enable', C.c_int),
+              ('smoothed_inlier_quantile', C.c_double), ('inner_patch_inlier_quantile', C.c_double),
+              ('rgb', vp), ('gt', vp), ('lossmult', vp), ('lm_c', C.c_int), ('loss_threshold', vp), ('denom', vp),
+              ('mask', vp), ('lossmult_out', vp), ('err', vp), ('stats', vp), ('mse', vp)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
@@ -212,6 +220,8 @@ _PROTOS = {
     'mnr_distortion_loss': ([f32, i64, i64, i32, vp, vp, vp, vp, vp], i32),
     'mnr_lossfun_outer': ([i64, i32, vp, vp, i32, vp, vp, vp, vp], i32),
     'mnr_lossfun_distortion': ([i64, i32, vp, vp, vp, vp], i32),
+    'mnr_robustnerf_mask': ([C.POINTER(RobustArgs), vp], i32),
+    'mnr_quantile': ([i64, vp, C.c_double, vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

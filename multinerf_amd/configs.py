@@ -286,6 +286,28 @@ Config.grad_max_norm = 0.1
 Config.grad_max_val = 0.1
 Config.adam_eps = 1e-8
 """,
+    # reference configs/360_robustnerf.gin
+    '360_robustnerf': """
+Config.dataset_loader = 'llff'
+Config.near = 0.2
+Config.far = 1e6
+Config.factor = 4
+Config.patch_size = 16
+Config.data_loss_type = 'robustnerf'
+Config.robustnerf_inlier_quantile = 0.8
+Config.enable_robustnerf_loss = True
+Model.raydist_fn = @jnp.reciprocal
+Model.opaque_background = True
+PropMLP.warp_fn = @coord.contract
+PropMLP.net_depth = 4
+PropMLP.net_width = 256
+PropMLP.disable_density_normals = True
+PropMLP.disable_rgb = True
+NerfMLP.warp_fn = @coord.contract
+NerfMLP.net_depth = 8
+NerfMLP.net_width = 1024
+NerfMLP.disable_density_normals = True
+""",
 }
 
 

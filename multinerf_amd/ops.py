@@ -991,6 +991,55 @@ def data_loss(loss_type, charb_padding, loss_mult, rgb, gt, lossmult, denom, sta
   return g
 
 
+def robustnerf_mask(rgb, gt, lossmult, loss_threshold, *, B_valid, patch_size, inner_patch_size, filter_size,
+                    smoothed_inlier_quantile, inner_patch_inlier_quantile, enable=True, mask=None, lossmult_out=None,
+                    err=None, stats=None, mse=None, denom=None):
+  """robustnerf.robustnerf_mask (robustnerf.py:23-86) for one level: rgb, gt [B,3], lossmult [B,1|3], loss_threshold a
+  device scalar; the first B_valid rays are [patch][y][x] pixels.  Returns (mask [B], lossmult * mask [B,lm_c]); `err`
+  [B] receives the per-pixel error, `stats` [4] += the means the reference logs, `mse` [1] += the level's mse over `denom`
+  with the unmasked lossmult.  Enqueues one launch, reads nothing back."""
+  for x, nm in ((rgb, 'rgb'), (gt, 'gt'), (lossmult, 'lossmult'), (loss_threshold, 'loss_threshold')):
+    _chk(x, f32, nm)
+  for x, nm in ((mask, 'mask'), (lossmult_out, 'lossmult_out'), (err, 'err'), (stats, 'stats'), (mse, 'mse'), (denom, 'denom')):
+    _chk(x, f32, nm, allow_none=True)
+  B = rgb.shape[0]
+  lm_c = lossmult.shape[-1]
+  if rgb.shape != (B, 3) or gt.shape != (B, 3) or lossmult.shape != (B, lm_c):
+    raise ValueError(f'robustnerf_mask: rgb {tuple(rgb.shape)}, gt {tuple(gt.shape)}, lossmult {tuple(lossmult.shape)} must be [B,3], [B,3], [B,1|3]')
+  if loss_threshold.numel() != 1:
+    raise ValueError('robustnerf_mask: loss_threshold must hold one value')
+  if mask is None:
+    mask = torch.empty((B,), dtype=f32, device=rgb.device)
+  if lossmult_out is None:
+    lossmult_out = torch.empty_like(lossmult)
+  if mask.numel() != B or lossmult_out.shape != lossmult.shape or (err is not None and err.numel() < B_valid):
+    raise ValueError('robustnerf_mask: mask [B], lossmult_out [B,lm_c] and err [B] must match the batch')
+  if (stats is not None and stats.numel() < 4) or (mse is not None and (mse.numel() < 1 or denom is None)):
+    raise ValueError('robustnerf_mask: stats needs 4 entries, mse one entry and denom')
+  a = L.RobustArgs()
+  a.B, a.B_valid = B, int(B_valid)
+  a.patch_size, a.inner_patch_size, a.filter_size, a.enable = int(patch_size), int(inner_patch_size), int(filter_size), int(bool(enable))
+  a.smoothed_inlier_quantile, a.inner_patch_inlier_quantile = float(smoothed_inlier_quantile), float(inner_patch_inlier_quantile)
+  p = lambda t: None if t is None else t.data_ptr()
+  a.rgb, a.gt, a.lossmult, a.lm_c, a.loss_threshold, a.denom = p(rgb), p(gt), p(lossmult), lm_c, p(loss_threshold), p(denom)
+  a.mask, a.lossmult_out, a.err, a.stats, a.mse = p(mask), p(lossmult_out), p(err), p(stats), p(mse)
+  L.check(lib().mnr_robustnerf_mask(C.byref(a), _stream()))
+  return mask, lossmult_out
+
+
+def quantile(x, q, out=None, *, N=None):
+  """jnp.quantile(x[:N], q) into the device scalar `out` (exact order statistics, linear interpolation; no host read)."""
+  _chk(x, f32, 'x')
+  _chk(out, f32, 'out', allow_none=True)
+  N = x.numel() if N is None else int(N)
+  if N > x.numel():
+    raise ValueError(f'quantile: N = {N} exceeds the {x.numel()} values of x')
+  if out is None:
+    out = torch.empty((1,), dtype=f32, device=x.device)
+  L.check(lib().mnr_quantile(N, _ptr(x), float(q), _ptr(out), _stream()))
+  return out
+
+
 def interlevel_loss(mult, t, w, t_env, w_env, stats, g_w_env, *, B_valid):
   for x, nm in ((t, 't'), (w, 'w'), (t_env, 't_env'), (w_env, 'w_env')):
     _chk(x, f32, nm)

@@ -66,8 +66,11 @@ def create_train_step(model: models.Model, config, dataset=None):
   # train_utils.py:234-237: the dataset names the projection; perspective without one.
   camtype = getattr(dataset, 'camtype', camera_utils.ProjectionType.PERSPECTIVE) if dataset is not None \
       else camera_utils.ProjectionType.PERSPECTIVE
-  if config.data_loss_type not in ('mse', 'charb', 'rawnerf'):
+  if config.data_loss_type not in ('mse', 'charb', 'rawnerf', 'robustnerf'):
     raise NotImplementedError(f'data_loss_type {config.data_loss_type!r} is out of scope')
+  robust = config.data_loss_type == 'robustnerf'
+  if robust and config.robustnerf_inner_patch_size > config.patch_size:
+    raise ValueError('patch_size must be larger than robustnerf_inner_patch_size.')          # robustnerf.py:34-36
   use_orient = config.orientation_loss_mult > 0 or config.orientation_coarse_loss_mult > 0
   use_prednorm = config.predicted_normal_loss_mult > 0 or config.predicted_normal_coarse_loss_mult > 0
   if config.orientation_loss_target not in ('normals', 'normals_pred'):
@@ -117,7 +120,9 @@ def create_train_step(model: models.Model, config, dataset=None):
     nlev = len(levels)
     # stats layout: [mse_l, data_l]*nlev | interlevel | distortion | denom | orientation | predicted_normals
     #               | disparity_mse_l * nlev | normal_mae_l * nlev | weight loss
-    stats = model._buf(('train', 'stats'), (4 * nlev + 6,), f32)
+    #               | robustnerf only: loss_threshold (the next step's) | is_inlier_loss | has_inlier_neighbors | is_inlier_patch | mask
+    nbase = 4 * nlev + 6
+    stats = model._buf(('train', 'stats'), (nbase + (5 if robust else 0),), f32)
     stats.zero_()
     denom = stats[2 * nlev + 2:2 * nlev + 3]
     lossmult = R.lossmult
@@ -138,10 +143,46 @@ def create_train_step(model: models.Model, config, dataset=None):
     g_w = [None] * nlev                                               # upstream d loss / d weights (Ref-NeRF normal losses only)
     data_spec, w_spec = [None] * nlev, [None] * nlev
     last = levels[-1]
+    robust_moves = []                                                 # [(from, to)]: data-loss terms the level kernels leave in scratch
+    if robust:
+      # train_utils.py:104-108 + robustnerf.py: the mask of every level whose data loss takes part, and of the final level for the
+      # logged means and the next step's threshold (the reference's stats.update keeps the last level's).  The masked loss
+      # sum(lossmult * mask * r^2) / sum(lossmult) is the level kernels' MSE branch on `lossmult * mask` under the unchanged
+      # denominator; what they report as mse is then the masked one and goes to scratch, the logged mse comes from the mask kernel.
+      pp = int(config.patch_size) ** 2
+      if B0 % pp != 0:
+        raise ValueError(f'robustnerf: {B0} rays are not a multiple of patch_size^2 = {pp}')
+      if torch.is_tensor(loss_threshold):
+        thr = loss_threshold.detach().to(device=dev, dtype=f32).reshape(1)
+      else:
+        thr = model._buf(('train', 'robust_thr'), (1,), f32)
+        thr.fill_(float(loss_threshold))
+      scratch = model._buf(('train', 'robust_scratch'), (2 * nlev,), f32)
+      scratch.zero_()
+      saved['robust'] = dict(threshold=thr, mask=[None] * nlev, lossmult=[None] * nlev, err=None)
     for li, lv in enumerate(levels):
       mult = config.data_loss_mult if li == nlev - 1 else config.data_coarse_loss_mult
       data_spec[li] = dict(type=config.data_loss_type, charb_padding=config.charb_padding, mult=mult, rgb_out=lv['rgb_out'],
                            gt=gt, lossmult=lossmult, denom=denom, stats=stats[2 * li:2 * li + 2])
+      if robust and (mult > 0 or li == nlev - 1):
+        fine = li == nlev - 1
+        err = model._buf(('train', 'robust_err'), (Bp,), f32) if fine else None
+        mask, lm_masked = ops.robustnerf_mask(
+            lv['rgb_out'], gt, lossmult, thr, B_valid=B0, patch_size=config.patch_size,
+            inner_patch_size=config.robustnerf_inner_patch_size, filter_size=config.robustnerf_smoothed_filter_size,
+            smoothed_inlier_quantile=config.robustnerf_smoothed_inlier_quantile,
+            inner_patch_inlier_quantile=config.robustnerf_inner_patch_inlier_quantile, enable=config.enable_robustnerf_loss,
+            mask=model._buf(('train', 'robust_mask', li), (Bp,), f32),
+            lossmult_out=model._buf(('train', 'robust_lm', li), tuple(lossmult.shape), f32), err=err,
+            stats=stats[nbase + 1:nbase + 5] if fine else None, mse=stats[2 * li:2 * li + 1], denom=denom)
+        if fine:
+          ops.quantile(err, config.robustnerf_inlier_quantile, out=stats[nbase:nbase + 1], N=B0)     # robustnerf.py:26-28
+          saved['robust']['err'] = err
+        saved['robust']['mask'][li], saved['robust']['lossmult'][li] = mask, lm_masked
+        data_spec[li].update(type='mse', lossmult=lm_masked, stats=scratch[2 * li:2 * li + 2])
+        robust_moves.append((scratch[2 * li + 1:2 * li + 2], stats[2 * li + 1:2 * li + 2]))
+      elif robust:
+        data_spec[li]['type'] = 'mse'                                  # no data loss on this level: its mse for the log
       if li < nlev - 1 and config.interlevel_loss_mult > 0:           # train_utils.py:139-150
         w_spec[li] = dict(mode='interlevel', mult=config.interlevel_loss_mult, sdist=lv['sdist'], t_ref=last['sdist'],
                           w_ref=last['weights'], stat=stats[2 * nlev:2 * nlev + 1])
@@ -206,7 +247,7 @@ def create_train_step(model: models.Model, config, dataset=None):
                              losses=dict(B_valid=B0, data=data_spec[li], weights=w_spec[li]))
       else:                                                            # no gradient reaches this level: its mse for the log
         d = data_spec[li]
-        ops.data_loss(d['type'], d['charb_padding'], d['mult'], d['rgb_out'], gt, lossmult, denom, d['stats'], B_valid=B0,
+        ops.data_loss(d['type'], d['charb_padding'], d['mult'], d['rgb_out'], gt, d['lossmult'], denom, d['stats'], B_valid=B0,
                       want_grad=False)
       if overlap and li == nlev - 1:
         for name, b, e in model.modules:
@@ -312,6 +353,8 @@ def create_train_step(model: models.Model, config, dataset=None):
         done_props.record(bs.prop)
       level_backward(nlev - 1)
       cur.wait_event(done_props)
+    for src, dst in robust_moves:
+      dst.copy_(src)
     if g_expo is not None:
       n_off = model.num_glo_embeddings * 3
       ops.exposure_scale_bwd(R.exposure_values.reshape(-1).contiguous().float(),
@@ -357,7 +400,7 @@ def create_train_step(model: models.Model, config, dataset=None):
 
     # (copies: `stats` and `sq` are workspace tensors the next step overwrites, and callers keep TrainStats in buffers)
     out_stats = {'_raw': stats.clone(), '_nlev': nlev, 'grad_sqnorms': sq.clone(), '_disp': config.compute_disp_metrics,
-                 '_normal': config.compute_normal_metrics}
+                 '_normal': config.compute_normal_metrics, '_robust': robust, '_robust_on': robust and config.enable_robustnerf_loss}
     if return_grads:
       out_stats['_grads'] = raw_grads
     if tree_stats:
@@ -370,6 +413,13 @@ def create_train_step(model: models.Model, config, dataset=None):
 
 class TrainStats(dict):
   """Lazy view of the device-side stats vector (no host sync until a value is read)."""
+
+  def loss_threshold_device(self):
+    """robustnerf: stats['loss_threshold'] (robustnerf.py:26-32, averaged over the ranks as train.py:129 does) as a 0-d device
+    tensor, for the next call's `loss_threshold`; no host read."""
+    if not self.get('_robust'):
+      raise KeyError("loss_threshold is a statistic of data_loss_type = 'robustnerf'")
+    return self['_raw'][4 * self['_nlev'] + 6]
 
   def materialize(self):
     raw = self['_raw'].detach().cpu().numpy()
@@ -394,6 +444,12 @@ class TrainStats(dict):
       out['normal_maes'] = raw[3 * n + 5:4 * n + 5]
     out['loss'] = sum(out['losses'].values())
     out['psnr'] = float(out['psnrs'][-1])
+    if self.get('_robust'):                                            # robustnerf.py:30-32,40,56,77,85
+      k = 4 * n + 6
+      out['loss_threshold'] = float(raw[k])
+      out['mask'] = float(raw[k + 4])
+      if self.get('_robust_on'):
+        out.update(is_inlier_loss=float(raw[k + 1]), has_inlier_neighbors=float(raw[k + 2]), is_inlier_patch=float(raw[k + 3]))
     # per top-level module, AFTER the clip by value (what clip_adam's norm clip sees); the reference logs the
     # pre-clip norm (train_utils.py:323-324): identical whenever grad_max_val = 0, as in every shipped config
     out['grad_norms'] = np.sqrt(self['grad_sqnorms'].detach().cpu().numpy())

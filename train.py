@@ -67,13 +67,17 @@ def main():
   gen = torch.Generator(device=dev).manual_seed(20200823 + rank)
   num_steps = config.early_exit_steps if config.early_exit_steps is not None else config.max_steps
   stats_buffer, train_start, total_time, total_steps = [], time.time(), 0.0, 0
+  robust = config.data_loss_type == 'robustnerf'
+  loss_threshold = 1.0                                                                   # train.py:109
   for step in range(init_step, num_steps + 1):
     batch = next(dataset)
     train_frac = float(np.clip((step - 1) / (config.max_steps - 1), 0, 1))              # train.py:118
     logging_step = step % config.print_every == 0 or step == num_steps
     # (the per-key statistics of train_utils.py:304,323-335 -- weight_l2s, grad_norms / maxes, opt_update_norms / maxes -- on the
     # steps that are logged: they cost two copies of the parameter vector)
-    state, stats, gen = train_pstep(gen, state, batch, cameras, train_frac, 1.0, tree_stats=logging_step)
+    state, stats, gen = train_pstep(gen, state, batch, cameras, train_frac, loss_threshold, tree_stats=logging_step)
+    if robust and config.enable_robustnerf_loss:                                         # train.py:128-129
+      loss_threshold = stats.loss_threshold_device()                                     # (stays on the device: no host read)
     stats_buffer.append(stats)
     if step % config.print_every == 0 or step == num_steps:                              # train.py:141-216
       # train.py:150-186: the logged numbers are AVERAGES over the steps since the last print
@@ -82,6 +86,9 @@ def main():
       s['loss'] = float(np.mean([m['loss'] for m in mats]))
       s['psnr'] = float(np.mean([m['psnr'] for m in mats]))
       s['losses'] = {k: float(np.mean([m['losses'][k] for m in mats])) for k in mats[-1]['losses']}
+      robust_keys = [k for k in ('loss_threshold', 'is_inlier_loss', 'has_inlier_neighbors', 'is_inlier_patch', 'mask') if k in mats[-1]]
+      for k in robust_keys:
+        s[k] = float(np.mean([m[k] for m in mats]))
       torch.cuda.synchronize()
       elapsed = time.time() - train_start
       steps_done = len(stats_buffer)
@@ -90,13 +97,14 @@ def main():
       total_steps += steps_done
       if rank == 0:
         msg = (f'{step}/{num_steps}: loss={s["loss"]:.5f}, psnr={s["psnr"]:.3f}, lr={lr_fn(step):.2e} | '
-               + ', '.join(f'{k}={v:.5f}' for k, v in s['losses'].items()) + f', {rays_per_sec:.0f} r/s')
+               + ', '.join(f'{k}={v:.5f}' for k, v in s['losses'].items())
+               + ''.join(f', {k}={s[k]:.5g}' for k in robust_keys) + f', {rays_per_sec:.0f} r/s')
         print(msg, flush=True)
         if log:
           tree = {k: {kk: float(vv) for kk, vv in s[k].items() if kk.count('/') == 0} for k in
                   ('weight_l2s', 'grad_norms', 'grad_maxes', 'opt_update_norms', 'opt_update_maxes') if isinstance(s.get(k), dict)}
           log.write(json.dumps(dict(step=step, loss=s['loss'], psnr=s['psnr'], lr=lr_fn(step), losses=s['losses'],
-                                    train_rays_per_sec=rays_per_sec, **tree)) + '\n')
+                                    train_rays_per_sec=rays_per_sec, **{k: s[k] for k in robust_keys}, **tree)) + '\n')
           log.flush()
       stats_buffer, train_start = [], time.time()
     if config.checkpoint_dir and rank == 0 and (step == 1 or step % config.checkpoint_every == 0):
