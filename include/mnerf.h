@@ -663,6 +663,72 @@ typedef struct {
 int mnr_clip_adam(const mnr_adam_cfg* cfg, int64_t begin, int64_t end, const float* sqnorm_seg,
                   const float* grad, float* params, float* mu, float* nu, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Evaluation metrics  (replaces internal/image.py: MetricHarness :127-141 with dm_pix.ssim, color_correct :81-124, and
+ * the quantise / crop / mean of eval.py:134-146).  Every sum is per-workgroup partials in float64 added by a second,
+ * fixed-order stage: no floating-point atomics, two runs agree bit for bit.  Results are device scalars in float64.
+ * ------------------------------------------------------------------------- */
+#define MNR_SSIM_MAX_FILTER 11
+
+/* dm_pix.ssim(a, b) of two [H,W,C] float32 images: Gaussian window of `filter_size` taps (odd, <= MNR_SSIM_MAX_FILTER)
+ * and `filter_sigma`, normalised to sum 1, applied separably per channel with VALID padding;
+ * mu0, mu1 the windowed means, sigma00 = filt(a a) - mu0^2 and sigma11 likewise, both clamped at float32_eps^2,
+ * sigma01 = filt(a b) - mu0 mu1 limited in magnitude to sqrt(sigma00 sigma11); c1 = (k1 max_val)^2, c2 = (k2 max_val)^2;
+ * ssim_map = (2 mu0 mu1 + c1)(2 sigma01 + c2) / ((mu0^2 + mu1^2 + c1)(sigma00 + sigma11 + c2)); *out = its mean.
+ * crop = c > 0 evaluates x[c:-c, c:-c] by index arithmetic.  One workgroup per 32 x 16 output tile and channel; window
+ * sums in float64.  `map` (may be NULL) receives ssim_map as [H - 2c - f + 1, W - 2c - f + 1, C] float32. */
+typedef struct {
+  int H, W, C, crop;
+  int filter_size;
+  double filter_sigma, max_val, k1, k2;
+  const float* a;
+  const float* b;
+  float* map;
+  double* partials;                /* workspace of mnr_ssim_partials(...) doubles */
+  double* out;                     /* [1] */
+} mnr_ssim_args;
+int mnr_ssim_partials(int H, int W, int C, int crop, int filter_size);    /* <= 0: the arguments are not valid */
+int mnr_ssim(const mnr_ssim_args* args, void* stream);
+
+/* out[0] = sum (q(a) - b)^2 over x[c:-c, c:-c] of two [H,W,C] images, in float64; quantize != 0: q(a) = rint(255 a) / 255
+ * (round half to even, np.round), else q(a) = a.  a / b are float64 when a_f64 / b_f64 is set, else float32.  q_out
+ * (may be NULL) receives q(a) of the WHOLE image as float32 (what mnr_ssim takes).  partials: workspace of
+ * mnr_image_sqdiff_partials(H * W * C) doubles. */
+typedef struct {
+  int H, W, C, crop, quantize, a_f64, b_f64;
+  const void* a;
+  const void* b;
+  float* q_out;
+  double* partials;
+  double* out;                     /* [1] */
+} mnr_sqdiff_args;
+int mnr_image_sqdiff_partials(int64_t n);
+int mnr_image_sqdiff(const mnr_sqdiff_args* args, void* stream);
+
+/* One iteration of image.color_correct (internal/image.py:95-122), left-hand side.  Per pixel the ten features
+ * r r, r g, r b, g g, g b, b b, r, g, b, 1 of img [N,3] (float64); per channel c, over the rows where
+ * mask0[:, c] & unclipped(img[:, c]) & unclipped(ref[:, c]) holds (unclipped(z): eps <= z <= 1 - eps), the symmetric
+ * A^T A and A^T b with b = ref[:, c].  out [3][65] float64: the 55 entries i <= j of A^T A in row-major order of the
+ * upper triangle, then the 10 of A^T b.  write_mask0 != 0: mask0 = unclipped(img) is WRITTEN (the first iteration,
+ * image.py:91) instead of read.  partials: workspace of mnr_cc_gram_partials(N) doubles. */
+#define MNR_CC_FEATURES 10
+#define MNR_CC_GRAM_OUT 65
+typedef struct {
+  int64_t N;
+  double eps;
+  const double* img;               /* [N,3] current corrected image */
+  const double* ref;               /* [N,3] */
+  unsigned char* mask0;            /* [N,3] */
+  int write_mask0;
+  double* partials;
+  double* out;                     /* [3][MNR_CC_GRAM_OUT] */
+} mnr_cc_gram_args;
+int mnr_cc_gram_partials(int64_t N);
+int mnr_cc_gram(const mnr_cc_gram_args* args, void* stream);
+
+/* out[i, c] = clip(sum_k feature_k(img[i]) warp[k][c], 0, 1) in float64 (image.py:121-122); out may alias img. */
+int mnr_cc_apply(int64_t N, const double* img, const double* warp /* host [10][3] */, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

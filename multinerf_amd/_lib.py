@@ -155,6 +155,26 @@ class RobustArgs(C.Structure):
               ('mask', vp), ('lossmult_out', vp), ('err', vp), ('stats', vp), ('mse', vp)]
 
 
+SSIM_MAX_FILTER = 11               # MNR_SSIM_MAX_FILTER
+CC_FEATURES, CC_GRAM_OUT = 10, 65  # MNR_CC_FEATURES, MNR_CC_GRAM_OUT
+
+
+class SsimArgs(C.Structure):
+  _fields_ = [('H', C.c_int), ('W', C.c_int), ('C', C.c_int), ('crop', C.c_int), ('filter_size', C.c_int),
+              ('filter_sigma', C.c_double), ('max_val', C.c_double), ('k1', C.c_double), ('k2', C.c_double),
+              ('a', vp), ('b', vp), ('map', vp), ('partials', vp), ('out', vp)]
+
+
+class SqdiffArgs(C.Structure):
+  _fields_ = [('H', C.c_int), ('W', C.c_int), ('C', C.c_int), ('crop', C.c_int), ('quantize', C.c_int),
+              ('a_f64', C.c_int), ('b_f64', C.c_int), ('a', vp), ('b', vp), ('q_out', vp), ('partials', vp), ('out', vp)]
+
+
+class CcGramArgs(C.Structure):
+  _fields_ = [('N', C.c_int64), ('eps', C.c_double), ('img', vp), ('ref', vp), ('mask0', vp), ('write_mask0', C.c_int),
+              ('partials', vp), ('out', vp)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
@@ -222,6 +242,13 @@ _PROTOS = {
     'mnr_lossfun_distortion': ([i64, i32, vp, vp, vp, vp], i32),
     'mnr_robustnerf_mask': ([C.POINTER(RobustArgs), vp], i32),
     'mnr_quantile': ([i64, vp, C.c_double, vp, vp], i32),
+    'mnr_ssim_partials': ([i32, i32, i32, i32, i32], i32),
+    'mnr_ssim': ([C.POINTER(SsimArgs), vp], i32),
+    'mnr_image_sqdiff_partials': ([i64], i32),
+    'mnr_image_sqdiff': ([C.POINTER(SqdiffArgs), vp], i32),
+    'mnr_cc_gram_partials': ([i64], i32),
+    'mnr_cc_gram': ([C.POINTER(CcGramArgs), vp], i32),
+    'mnr_cc_apply': ([i64, vp, C.POINTER(C.c_double), vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

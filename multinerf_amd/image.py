@@ -1,0 +1,187 @@
+"""Functions for processing and scoring images (reference internal/image.py, and the per-image part of eval.py:118-163).
+
+Images are device tensors and stay there: the sums behind PSNR, SSIM and the colour correction's normal equations are
+HIP kernels (csrc/metrics.hip, through multinerf_amd.ops); what crosses to the host is scalars, and per colour-correction
+iteration three 10 x 10 systems.  There is no CPU fallback: a host tensor is refused.
+"""
+
+import math
+
+import numpy as np
+import torch
+
+from multinerf_amd import ops
+
+_F32_EPS = float(np.finfo(np.float32).eps)
+
+
+def mse_to_psnr(mse):
+  """Compute PSNR given an MSE (we assume the maximum pixel value is 1)."""
+  if isinstance(mse, torch.Tensor):
+    return -10. / math.log(10.) * torch.log(mse)
+  return -10. / math.log(10.) * math.log(mse) if mse > 0 else math.inf
+
+
+def psnr_to_mse(psnr):
+  """Compute MSE given a PSNR (we assume the maximum pixel value is 1)."""
+  if isinstance(psnr, torch.Tensor):
+    return torch.exp(-0.1 * math.log(10.) * psnr)
+  return math.exp(-0.1 * math.log(10.) * psnr)
+
+
+def ssim_to_dssim(ssim):
+  """Compute DSSIM given an SSIM."""
+  return (1 - ssim) / 2
+
+
+def dssim_to_ssim(dssim):
+  """Compute DSSIM given an SSIM."""
+  return 1 - 2 * dssim
+
+
+def linear_to_srgb(linear, eps=None):
+  """Assumes `linear` is in [0, 1], see https://en.wikipedia.org/wiki/SRGB."""
+  if eps is None:
+    eps = _F32_EPS
+  srgb0 = 323 / 25 * linear
+  srgb1 = (211 * torch.clamp(linear, min=eps)**(5 / 12) - 11) / 200
+  return torch.where(linear <= 0.0031308, srgb0, srgb1)
+
+
+def srgb_to_linear(srgb, eps=None):
+  """Assumes `srgb` is in [0, 1], see https://en.wikipedia.org/wiki/SRGB."""
+  if eps is None:
+    eps = _F32_EPS
+  linear0 = 25 / 323 * srgb
+  linear1 = torch.clamp((200 * srgb + 11) / 211, min=eps)**(12 / 5)
+  return torch.where(srgb <= 0.04045, linear0, linear1)
+
+
+def downsample(img, factor):
+  """Area downsample img (factor must evenly divide img height and width)."""
+  sh = tuple(img.shape)
+  if not (sh[0] % factor == 0 and sh[1] % factor == 0):
+    raise ValueError(f'Downsampling factor {factor} does not evenly divide image shape {sh[:2]}')
+  img = img.reshape((sh[0] // factor, factor, sh[1] // factor, factor) + sh[2:])
+  return img.mean((1, 3))
+
+
+def solve_warp(gram):
+  """The [10,3] warp of one colour-correction iteration from the kernel's [3,65] sums: per channel
+  numpy.linalg.lstsq(A^T A, A^T b) in float64.  lstsq and not solve: a grey image makes the system rank deficient, and
+  the minimum-norm solution of the normal equations is the one lstsq on the [pixels, 10] system gives."""
+  gram = np.asarray(gram, np.float64)
+  iu = np.triu_indices(10)
+  warp = np.empty((10, 3))
+  for c in range(3):
+    G = np.zeros((10, 10))
+    G[iu] = gram[c, :55]
+    G = G + np.triu(G, 1).T
+    w = np.linalg.lstsq(G, gram[c, 55:], rcond=None)[0]
+    assert np.all(np.isfinite(w))
+    warp[:, c] = w
+  return warp
+
+
+def color_correct(img, ref, num_iters=5, eps=0.5 / 255):
+  """Warp `img` to match the colors in `ref_img` (image.py:81-124): a quadratic colour transform fitted by least squares
+  over the unsaturated pixels, five times.  Device tensors of any float type; the result is float64, the precision the
+  reference's eval.py:118-123 runs it in."""
+  if img.shape[-1] != ref.shape[-1]:
+    raise ValueError(f'img\'s {img.shape[-1]} and ref\'s {ref.shape[-1]} channels must match')
+  if img.shape[-1] != 3 or img.shape != ref.shape:
+    raise ValueError(f'color_correct: needs two RGB images of one shape, got {tuple(img.shape)} and {tuple(ref.shape)}')
+  if not (ops._on_device(img) and ops._on_device(ref)):
+    raise ValueError('color_correct: img and ref must be device tensors (the HIP path has no CPU fallback)')
+  img_mat = img.reshape(-1, 3).to(torch.float64).contiguous()
+  if img_mat.data_ptr() == img.data_ptr():
+    img_mat = img_mat.clone()                                   # (updated in place below)
+  ref_mat = ref.reshape(-1, 3).to(torch.float64).contiguous()
+  mask0 = torch.empty(img_mat.shape, dtype=torch.uint8, device=img_mat.device)
+  gram = torch.empty((3, 65), dtype=torch.float64, device=img_mat.device)
+  for it in range(num_iters):
+    ops.cc_gram(img_mat, ref_mat, mask0, eps, write_mask0=(it == 0), out=gram)
+    warp = solve_warp(gram.cpu().numpy())
+    ops.cc_apply(img_mat, warp, out=img_mat)
+  return img_mat.reshape(img.shape)
+
+
+class MetricHarness:
+  """A helper class for evaluating several error metrics (image.py:127-141): PSNR and dm_pix.ssim.
+
+  `quantize` and `crop` fold eval.py:134-143 into the kernels: the prediction is rounded to 8 bits (np.round) and both
+  images are cropped by `crop` pixels at every border, by index arithmetic, before either metric is taken."""
+
+  def __call__(self, rgb_pred, rgb_gt, name_fn=lambda s: s, *, quantize=False, crop=0):
+    """Evaluate the error between a predicted rgb image and the true image."""
+    if rgb_pred.dim() != 3 or rgb_pred.shape != rgb_gt.shape:
+      raise ValueError(f'MetricHarness: needs two [H,W,C] images of one shape, got {tuple(rgb_pred.shape)} and {tuple(rgb_gt.shape)}')
+    pred = rgb_pred.contiguous()
+    gt = rgb_gt.contiguous()
+    if quantize or pred.dtype != torch.float32:             # SSIM takes the float32 image the statistics pass writes
+      pred32 = torch.empty(pred.shape, dtype=torch.float32, device=pred.device)
+      sq = ops.image_sqdiff(pred, gt, quantize=quantize, crop=crop, q_out=pred32)
+    else:
+      pred32 = pred
+      sq = ops.image_sqdiff(pred, gt, crop=crop)
+    gt32 = gt if gt.dtype == torch.float32 else gt.to(torch.float32)
+    ssim = ops.ssim(pred32, gt32, crop=crop)
+    h, w, c = pred.shape
+    both = torch.cat([sq, ssim]).cpu()
+    psnr = float(mse_to_psnr(float(both[0]) / ((h - 2 * crop) * (w - 2 * crop) * c)))
+    return {
+        name_fn('psnr'): psnr,
+        name_fn('ssim'): float(both[1]),
+    }
+
+
+def quantize_u8(img):
+  """The uint8 host image np.round(img * 255) of a device image in [0, 1]: what eval_quantize_metrics scores."""
+  return np.clip(np.rint(img.detach().to(torch.float64).cpu().numpy() * 255.0), 0, 255).astype(np.uint8)
+
+
+def evaluate_image(rendering, batch, config, metric_harness=None):
+  """What the reference's eval.py:118-163 does with one rendered test image, in that order: colour-correct the rendering
+  against the ground truth in float64, quantise both versions to 8 bits (Config.eval_quantize_metrics), crop the borders
+  (Config.eval_crop_borders), PSNR + SSIM of each, then the disparity and normal metrics.
+
+  rendering: the dict of models.render_image ([H,W,...] device tensors); batch: the test batch (rgb, and disps / normals /
+  alphas where the metrics need them).  Returns (metric, metric_cc, images_to_save); rendering['rgb_cc'] is added as the
+  reference does.  images_to_save maps the reference's file stems (color, color_cc, distance_mean, distance_median,
+  normals, acc) to device tensors."""
+  if config.eval_raw_affine_cc:
+    raise ValueError('Config.eval_raw_affine_cc = True is not supported: raw_utils.match_images_affine and the raw '
+                     'post-processing need the DNG metadata of the RawNeRF loader')
+  if metric_harness is None:
+    metric_harness = MetricHarness()
+  gt_rgb = batch.rgb[..., :3].to(torch.float64)                                      # eval.py:119-120
+  rgb = rendering['rgb'].to(torch.float64)
+  rendering['rgb_cc'] = color_correct(rgb, gt_rgb)                                   # :123
+  quant, crop = bool(config.eval_quantize_metrics), int(config.eval_crop_borders)
+  metric = metric_harness(rgb, gt_rgb, quantize=quant, crop=crop)                    # :134-145
+  metric_cc = metric_harness(rendering['rgb_cc'], gt_rgb, quantize=quant, crop=crop)
+  n = rgb.shape[0] * rgb.shape[1]
+  flat = lambda x, c=None: x.reshape((n,) if c is None else (n, c)).to(torch.float32).contiguous()
+  if config.compute_disp_metrics:                                                    # :148-154
+    if getattr(batch, 'disps', None) is None:
+      raise ValueError('compute_disp_metrics needs batch.disps')
+    for tag in ('mean', 'median'):
+      key = f'distance_{tag}'
+      if rendering.get(key) is not None:
+        out = torch.zeros(1, dtype=torch.float32, device=rgb.device)
+        ops.render_metrics(n, distance_mean=flat(rendering[key]), disps=flat(batch.disps), out_disp=out)
+        metric[f'disparity_{tag}_mse'] = float(out.cpu()[0])
+  if config.compute_normal_metrics:                                                  # :156-163
+    if getattr(batch, 'normals', None) is None or getattr(batch, 'alphas', None) is None:
+      raise ValueError('compute_normal_metrics needs batch.normals and batch.alphas')
+    for key, val in list(rendering.items()):
+      if key.startswith('normals') and val is not None:
+        out = torch.zeros(1, dtype=torch.float32, device=rgb.device)
+        ops.render_metrics(n, acc=flat(rendering['acc']), alphas=flat(batch.alphas), normals=flat(val, 3),
+                           normals_gt=flat(batch.normals, 3), out_normal=out)        # (train_utils' weighted MAE kernel)
+        metric[key + '_mae'] = float(out.cpu()[0])
+  images = {'color': rendering['rgb'], 'color_cc': rendering['rgb_cc']}              # :171-188
+  for key in ('distance_mean', 'distance_median', 'normals', 'acc'):
+    if rendering.get(key) is not None:
+      images[key] = rendering[key]
+  return metric, metric_cc, images

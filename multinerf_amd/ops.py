@@ -1040,6 +1040,108 @@ def quantile(x, q, out=None, *, N=None):
   return out
 
 
+# ----------------------------------------------------------------------------- evaluation metrics (csrc/metrics.hip)
+
+f64 = torch.float64
+
+
+def _image_pair(a, b, name, dtypes):
+  for x, nm in ((a, 'a'), (b, 'b')):
+    if x is None:
+      raise ValueError(f'{name}: {nm} is None')
+    if not _on_device(x):
+      raise ValueError(f'{name}: {nm} must be a device tensor (the HIP path has no CPU fallback)')
+    if x.dtype not in dtypes:
+      raise ValueError(f'{name}: {nm} must be one of {dtypes}, is {x.dtype}')
+    if not x.is_contiguous():
+      raise ValueError(f'{name}: {nm} must be contiguous')
+  if a.dim() != 3 or a.shape != b.shape:
+    raise ValueError(f'{name}: needs two [H,W,C] images of one shape, got {tuple(a.shape)} and {tuple(b.shape)}')
+
+
+def ssim(a, b, *, max_val=1.0, filter_size=11, filter_sigma=1.5, k1=0.01, k2=0.03, crop=0, return_map=False, out=None):
+  """dm_pix.ssim(a, b) of two [H,W,C] float32 device images, over x[crop:-crop, crop:-crop] when crop > 0.  Returns the
+  mean as a float64 device scalar [1] (and the [H', W', C] float32 SSIM map with return_map).  Two launches, no host read."""
+  _image_pair(a, b, 'ssim', (f32,))
+  _chk(out, f64, 'out', allow_none=True)
+  H, W, Cn = (int(v) for v in a.shape)
+  n_part = lib().mnr_ssim_partials(H, W, Cn, int(crop), int(filter_size))
+  args = L.SsimArgs()
+  args.H, args.W, args.C, args.crop, args.filter_size = H, W, Cn, int(crop), int(filter_size)
+  args.filter_sigma, args.max_val, args.k1, args.k2 = float(filter_sigma), float(max_val), float(k1), float(k2)
+  partials = torch.empty((max(n_part, 1),), dtype=f64, device=a.device)
+  if out is None:
+    out = torch.empty((1,), dtype=f64, device=a.device)
+  smap = None
+  if return_map and n_part > 0:
+    smap = torch.empty((H - 2 * int(crop) - int(filter_size) + 1, W - 2 * int(crop) - int(filter_size) + 1, Cn), dtype=f32,
+                       device=a.device)
+  args.a, args.b, args.map, args.partials, args.out = a.data_ptr(), b.data_ptr(), None if smap is None else smap.data_ptr(), \
+      partials.data_ptr(), out.data_ptr()
+  L.check(lib().mnr_ssim(C.byref(args), _stream()))          # (invalid shapes / filters are reported by the library)
+  return (out, smap) if return_map else out
+
+
+def image_sqdiff(a, b, *, quantize=False, crop=0, q_out=None, out=None):
+  """sum (q(a) - b)^2 over x[crop:-crop, crop:-crop] of two [H,W,C] device images (float32 or float64 each) as a float64
+  device scalar [1]; quantize: q(a) = rint(255 a) / 255.  q_out ([H,W,C] float32) receives q(a) of the whole image."""
+  _image_pair(a, b, 'image_sqdiff', (f32, f64))
+  _chk(q_out, f32, 'q_out', allow_none=True)
+  _chk(out, f64, 'out', allow_none=True)
+  if q_out is not None and q_out.shape != a.shape:
+    raise ValueError(f'image_sqdiff: q_out {tuple(q_out.shape)} must have the shape of a {tuple(a.shape)}')
+  H, W, Cn = (int(v) for v in a.shape)
+  args = L.SqdiffArgs()
+  args.H, args.W, args.C, args.crop, args.quantize = H, W, Cn, int(crop), int(bool(quantize))
+  args.a_f64, args.b_f64 = int(a.dtype == f64), int(b.dtype == f64)
+  partials = torch.empty((max(lib().mnr_image_sqdiff_partials(a.numel()), 1),), dtype=f64, device=a.device)
+  if out is None:
+    out = torch.empty((1,), dtype=f64, device=a.device)
+  args.a, args.b, args.q_out, args.partials, args.out = a.data_ptr(), b.data_ptr(), None if q_out is None else q_out.data_ptr(), \
+      partials.data_ptr(), out.data_ptr()
+  L.check(lib().mnr_image_sqdiff(C.byref(args), _stream()))
+  return out
+
+
+def cc_gram(img, ref, mask0, eps, *, write_mask0=False, out=None):
+  """One colour-correction iteration's normal equations (image.color_correct, image.py:95-116): img, ref [N,3] float64,
+  mask0 [N,3] uint8 (written when write_mask0).  Returns [3,65] float64 on the device: per channel the upper triangle of
+  A^T A (55, row-major) and A^T b (10)."""
+  _chk(img, f64, 'img')
+  _chk(ref, f64, 'ref')
+  _chk(mask0, torch.uint8, 'mask0')
+  _chk(out, f64, 'out', allow_none=True)
+  N = img.shape[0]
+  if img.shape != (N, 3) or ref.shape != (N, 3) or mask0.shape != (N, 3):
+    raise ValueError(f'cc_gram: img {tuple(img.shape)}, ref {tuple(ref.shape)} and mask0 {tuple(mask0.shape)} must be [N,3]')
+  args = L.CcGramArgs()
+  args.N, args.eps, args.write_mask0 = N, float(eps), int(bool(write_mask0))
+  partials = torch.empty((max(lib().mnr_cc_gram_partials(N), 1),), dtype=f64, device=img.device)
+  if out is None:
+    out = torch.empty((3, L.CC_GRAM_OUT), dtype=f64, device=img.device)
+  args.img, args.ref, args.mask0, args.partials, args.out = img.data_ptr(), ref.data_ptr(), mask0.data_ptr(), partials.data_ptr(), \
+      out.data_ptr()
+  L.check(lib().mnr_cc_gram(C.byref(args), _stream()))
+  return out
+
+
+def cc_apply(img, warp, out=None):
+  """clip(A(img) @ warp, 0, 1) in float64 (image.py:121-122): img [N,3] float64 on the device, warp [10,3] on the host
+  (a sequence or array of floats).  out may be img itself."""
+  _chk(img, f64, 'img')
+  _chk(out, f64, 'out', allow_none=True)
+  N = img.shape[0]
+  if img.shape != (N, 3) or (out is not None and out.shape != img.shape):
+    raise ValueError(f'cc_apply: img {tuple(img.shape)} (and out) must be [N,3]')
+  flat = [float(v) for row in warp for v in row]
+  if len(flat) != 3 * L.CC_FEATURES:
+    raise ValueError(f'cc_apply: warp must be [10,3], has {len(flat)} values')
+  if out is None:
+    out = torch.empty_like(img)
+  L.check(lib().mnr_cc_apply(N, _ptr(img), (C.c_double * len(flat))(*flat), _ptr(out), _stream()))
+  return out
+
+
 def interlevel_loss(mult, t, w, t_env, w_env, stats, g_w_env, *, B_valid):
   for x, nm in ((t, 't'), (w, 'w'), (t_env, 't_env'), (w_env, 'w_env')):
     _chk(x, f32, nm)

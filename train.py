@@ -19,7 +19,7 @@ import time
 import numpy as np
 import torch
 
-from multinerf_amd import checkpoints, configs, datasets, models, train_utils, utils
+from multinerf_amd import checkpoints, configs, datasets, models, ops, train_utils, utils
 from multinerf_amd import dist as mdist
 
 
@@ -118,10 +118,14 @@ def main():
       if rank == 0:
         h, w = rendering['rgb'].shape[:2]
         psnr = mse_to_psnr(float(((rendering['rgb'] - test_case.rgb)**2).mean()))
-        print(f'Eval {step}: {time.time() - t0:.3f}s, {h * w / (time.time() - t0):.0f} rays/sec, test psnr {psnr:.3f}',
-              flush=True)
+        extra = {}
+        if min(h, w) >= 11:                                  # (an image smaller than the 11 x 11 window has no SSIM)
+          extra['test_ssim'] = float(ops.ssim(rendering['rgb'].float().contiguous(),
+                                              test_case.rgb[..., :3].float().contiguous()).cpu()[0])   # train.py:240
+        print(f'Eval {step}: {time.time() - t0:.3f}s, {h * w / (time.time() - t0):.0f} rays/sec, test psnr {psnr:.3f}'
+              + ''.join(f', ssim {v:.4f}' for v in extra.values()), flush=True)
         if log:
-          log.write(json.dumps(dict(step=step, test_psnr=psnr)) + '\n')
+          log.write(json.dumps(dict(step=step, test_psnr=psnr, **extra)) + '\n')
           log.flush()
   if config.checkpoint_dir and rank == 0 and config.max_steps % config.checkpoint_every != 0:
     checkpoints.save_checkpoint(config.checkpoint_dir, model, state, int(state.step), keep=100, overwrite=True)   # train.py:284-287
