@@ -181,6 +181,14 @@ int mnr_pixels_to_rays(int64_t B, const int32_t* pix_x_int, const int32_t* pix_y
                        const float* pixtocam_ndc, int camtype, float* origins, float* directions, float* viewdirs,
                        float* radii, float* imageplane, void* stream);
 
+/* Rays of a spherical (panorama) camera, camera_utils.cast_spherical_rays (camera_utils.py:716-764): pixel (h, w) looks
+ * along the direction at theta = linspace(0, 2 pi, W + 1)[w], phi = linspace(0, pi, H + 1)[h] (y up), rotated by
+ * camtoworld [3,4] (fp32, device); radii from the forward differences to (h, w + 1) and (h + 1, w).  One thread per pixel
+ * recomputes its three grid directions in float64 and rounds once.  Outputs fp32 device: origins, directions, viewdirs
+ * [H,W,3] (viewdirs = directions: unit already), radii [H,W], imageplane [H,W,2] = 0. */
+int mnr_spherical_rays(int H, int W, const float* camtoworld, float* origins, float* directions, float* viewdirs,
+                       float* radii, float* imageplane, void* stream);
+
 /* GLO vectors (models.py:101-110,565-568): dst[b*n+i, col0+g] = table[cam_idx[b], g] (bf16), or 0 when
  * cam_idx is NULL (zero_glo=True).  table [num_embeddings, G] fp32 = params['Embed_0']['embedding']. */
 int mnr_glo_fill(int64_t B, int n, int G, const float* table, const int32_t* cam_idx, int num_embeddings,
@@ -728,6 +736,66 @@ int mnr_cc_gram(const mnr_cc_gram_args* args, void* stream);
 
 /* out[i, c] = clip(sum_k feature_k(img[i]) warp[k][c], 0, 1) in float64 (image.py:121-122); out may alias img. */
 int mnr_cc_apply(int64_t N, const double* img, const double* warp /* host [10][3] */, double* out, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Visualisation  (the per-pixel work of internal/vis.py and of render.py:86-93; csrc/vis.hip)
+ * float32 device images in, float64 arithmetic, one rounding at the store.
+ * ------------------------------------------------------------------------- */
+#define MNR_VIS_MAX_PERCENTILES 4
+
+/* vis.weighted_percentile(x, w, ps) (vis.py:22-30) on ordered data: x_sorted [N] ascending, order [N] (int64) the index
+ * every sorted value had before the sort, w [NW] the weights as given.  The weight of sorted element i is
+ * w[min(order[i], NW - 1)] (jax clamps an out-of-range gather index; visualize_suite's depth triplet has N = 3 NW).
+ * acc = running sum of those weights in float64, T = p acc[-1] / 100, out[k] = np.interp(T, acc, x_sorted): x[0] if
+ * T < acc[0], x[-1] if T >= acc[-1], else with j the LAST index that has acc[j] <= T,
+ * x[j] + (T - acc[j]) / (acc[j+1] - acc[j]) (x[j+1] - x[j]).  ps: HOST array of num_p <= 4 percentiles in [0, 100].
+ * out [num_p] fp32 device.  partials: mnr_weighted_percentile_partials(N) doubles of device workspace.  Fixed-order sums,
+ * no floating-point atomics: deterministic.  Any N >= 1; weights >= 0. */
+int mnr_weighted_percentile_partials(int64_t N);
+int mnr_weighted_percentile(int64_t N, const float* x_sorted, const int64_t* order, int64_t NW, const float* w, int num_p,
+                            const double* ps, double* partials, float* out, void* stream);
+
+/* x; log(x + eps32) and -log(x + eps32) (vis.visualize_suite's depth curves); log(x) (Config.render_dist_curve_fn) */
+typedef enum { MNR_VIS_CURVE_IDENTITY = 0, MNR_VIS_CURVE_LOG = 1, MNR_VIS_CURVE_NEG_LOG = 2, MNR_VIS_CURVE_LN = 3 } mnr_vis_curve;
+
+/* The per-pixel part of vis.visualize_cmap (vis.py:85-106): curve value, lo and hi; v = nan_to_num(clip((value -
+ * min(lo, hi)) / |hi - lo|, 0, 1)), or mod(value, modulus) / modulus when modulus > 0; with a LUT (C = 1) the colour is
+ * lut[min(trunc(v n_lut), n_lut - 1)], without (C = 3) the three normalised channels; with acc the result is matted over
+ * the checker as mnr_vis_matte does.  out_u8 = trunc(clip(nan_to_num(colour), 0, 1) 255) (render.py:93). */
+typedef struct {
+  int H, W, C;
+  const float* value;              /* [H,W,C] */
+  const float* lohi;               /* device [2]: lo, hi BEFORE the curve; may be NULL when modulus > 0 */
+  int curve;                       /* mnr_vis_curve */
+  double modulus;                  /* <= 0: none */
+  const float* lut;                /* [n_lut,3] or NULL */
+  int n_lut;
+  const float* acc;                /* [H,W] or NULL: no matte */
+  float dark, light;
+  int width;
+  float* out;                      /* [H,W,3], may be NULL when out_u8 is given */
+  unsigned char* out_u8;           /* [H,W,3] or NULL */
+} mnr_vis_cmap_args;
+int mnr_vis_cmap(const mnr_vis_cmap_args* args, void* stream);
+
+/* vis.matte (vis.py:39-45): out = pre(x) acc + bg (1 - acc), bg = light where (row % 2w) / w xor (col % 2w) / w, else dark.
+ * pre: x; x / 2 + 0.5 (normals); tanh(x) (roughness); ((origins + directions distance + 1) mod 2) / 2
+ * (visualize_coord_mod, vis.py:109-111,185; C = 3, x unused; directions and distance may both be NULL: origins are the
+ * coordinates). */
+typedef enum { MNR_VIS_PRE_NONE = 0, MNR_VIS_PRE_HALF = 1, MNR_VIS_PRE_TANH = 2, MNR_VIS_PRE_COORD_MOD = 3 } mnr_vis_preop;
+typedef struct {
+  int H, W, C;
+  int preop;                       /* mnr_vis_preop */
+  const float* x;                  /* [H,W,C] */
+  const float* acc;                /* [H,W] */
+  const float* origins;            /* [H,W,3], MNR_VIS_PRE_COORD_MOD only */
+  const float* directions;         /* [H,W,3] */
+  const float* distance;           /* [H,W] */
+  float dark, light;
+  int width;
+  float* out;                      /* [H,W,C] */
+} mnr_vis_matte_args;
+int mnr_vis_matte(const mnr_vis_matte_args* args, void* stream);
 
 #ifdef __cplusplus
 }

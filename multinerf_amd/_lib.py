@@ -175,6 +175,22 @@ class CcGramArgs(C.Structure):
               ('partials', vp), ('out', vp)]
 
 
+VIS_MAX_PERCENTILES = 4            # MNR_VIS_MAX_PERCENTILES
+VIS_CURVE = {None: 0, 'identity': 0, 'log': 1, 'neg_log': 2, 'ln': 3}
+VIS_PREOP = {None: 0, 'none': 0, 'half': 1, 'tanh': 2, 'coord_mod': 3}
+
+
+class VisCmapArgs(C.Structure):
+  _fields_ = [('H', C.c_int), ('W', C.c_int), ('C', C.c_int), ('value', vp), ('lohi', vp), ('curve', C.c_int),
+              ('modulus', C.c_double), ('lut', vp), ('n_lut', C.c_int), ('acc', vp), ('dark', C.c_float), ('light', C.c_float),
+              ('width', C.c_int), ('out', vp), ('out_u8', vp)]
+
+
+class VisMatteArgs(C.Structure):
+  _fields_ = [('H', C.c_int), ('W', C.c_int), ('C', C.c_int), ('preop', C.c_int), ('x', vp), ('acc', vp), ('origins', vp),
+              ('directions', vp), ('distance', vp), ('dark', C.c_float), ('light', C.c_float), ('width', C.c_int), ('out', vp)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
@@ -197,6 +213,7 @@ _PROTOS = {
     'mnr_sdist_bwd': ([C.POINTER(SdistBwdArgs), vp], i32),
     'mnr_viewdir_enc_fill': ([i64, i32, vp, i32, vp, i32, i32, i32, vp], i32),
     'mnr_pixels_to_rays': ([i64, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),
+    'mnr_spherical_rays': ([i32, i32, vp, vp, vp, vp, vp, vp, vp], i32),
     'mnr_glo_fill': ([i64, i32, i32, vp, vp, i32, vp, i32, i32, vp], i32),
     'mnr_glo_bwd': ([i64, i32, i32, vp, vp, vp, i32, vp, vp], i32),
     'mnr_gemm_nt_bf16': ([C.POINTER(GemmNTArgs), vp], i32),
@@ -249,6 +266,10 @@ _PROTOS = {
     'mnr_cc_gram_partials': ([i64], i32),
     'mnr_cc_gram': ([C.POINTER(CcGramArgs), vp], i32),
     'mnr_cc_apply': ([i64, vp, C.POINTER(C.c_double), vp, vp], i32),
+    'mnr_weighted_percentile_partials': ([i64], i32),
+    'mnr_weighted_percentile': ([i64, vp, vp, i64, vp, i32, C.POINTER(C.c_double), vp, vp, vp], i32),
+    'mnr_vis_cmap': ([C.POINTER(VisCmapArgs), vp], i32),
+    'mnr_vis_matte': ([C.POINTER(VisMatteArgs), vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

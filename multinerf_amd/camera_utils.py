@@ -1,7 +1,9 @@
 """Ray generation on device: the reference's camera_utils.pixels_to_rays / cast_ray_batch
 (internal/camera_utils.py:514-688) behind the same names, backed by mnr_pixels_to_rays (csrc/camera.hip).
 
-Only the per-pixel leaves are here; pose utilities / camera paths stay out of scope.
+The per-pixel leaves are device code, as are the rays of the spherical camera (mnr_spherical_rays); the
+pose utilities and the render paths (spiral, ellipse, spline: camera_utils.py:159-395) run once per script on the host, in
+NumPy float64.
 """
 
 import ctypes as C
@@ -80,6 +82,14 @@ def cast_ray_batch(cameras, pixels, camtype=ProjectionType.PERSPECTIVE, xnp=None
   return utils.Rays(origins=origins, directions=directions, viewdirs=viewdirs, radii=radii, imageplane=imageplane,
                     lossmult=pixels.lossmult, near=pixels.near, far=pixels.far, cam_idx=pixels.cam_idx,
                     exposure_idx=pixels.exposure_idx, exposure_values=pixels.exposure_values)
+
+
+def cast_spherical_rays(camtoworld, height, width, near, far, xnp=None):
+  """camera_utils.py:716-764: the rays of a spherical (panorama) camera, shaped [H, W, .] (`xnp` is accepted and ignored)."""
+  origins, directions, viewdirs, radii, imageplane = ops.spherical_rays(camtoworld, height, width)
+  full = lambda v, dt=torch.float32: torch.full((int(height), int(width), 1), v, dtype=dt, device=origins.device)
+  return utils.Rays(origins=origins, directions=directions, viewdirs=viewdirs, radii=radii, imageplane=imageplane,
+                    lossmult=full(1.), near=full(float(near)), far=full(float(far)), cam_idx=full(0, torch.int32))
 
 
 def intrinsic_matrix(fx, fy, cx, cy):
@@ -194,3 +204,123 @@ def transform_poses_pca(poses):
   out[:, :, 3] *= shrink
   world_to_pca[:3] *= shrink
   return out, world_to_pca
+
+
+# ----------------------------------------------------------------------------- render paths (host, NumPy float64)
+
+NEAR_STRETCH = .9                 # push the near bound forward for the forward-facing path (camera_utils.py:154-156)
+FAR_STRETCH = 5.                  # push the far bound back
+FOCUS_DISTANCE = .75              # weight of the far bound, in disparity, in the focus depth
+
+_F32_EPS = float(np.finfo(np.float32).eps)
+
+
+def generate_spiral_path(poses, bounds, n_frames=120, n_rots=2, zrate=.5):
+  """A forward-facing spiral (camera_utils.py:159-188): cameras circle in the average camera's x-y plane, with radii at the
+  90th percentile of the capture positions, and all look at one point on the average optical axis.  Its depth is a
+  weighted mean, in disparity, of the stretched near and far bounds."""
+  near_bound = bounds.min() * NEAR_STRETCH
+  far_bound = bounds.max() * FAR_STRETCH
+  focal = 1 / ((1 - FOCUS_DISTANCE) / near_bound + FOCUS_DISTANCE / far_bound)
+  radii = np.concatenate([np.percentile(np.abs(poses[:, :3, 3]), 90, 0), [1.]])
+  cam2world = average_pose(poses)
+  up = poses[:, :3, 1].mean(0)
+  lookat = cam2world @ [0, 0, -focal, 1.]
+  path = []
+  for theta in np.linspace(0., 2. * np.pi * n_rots, n_frames, endpoint=False):
+    position = cam2world @ (radii * [np.cos(theta), -np.sin(theta), -np.sin(theta * zrate), 1.])
+    path.append(viewmatrix(position - lookat, up, position))
+  return np.stack(path, axis=0)
+
+
+def _invert_step_cdf(t, log_w, n):
+  """stepfun.sample(None, t, log_w, n) (stepfun.py:153-211, math.py:108-127): n points that split the mass of the step
+  function (t [m + 1], weights softmax(log_w) [m]) evenly: the inverse CDF at u = linspace(0, 1 - eps32, n), no jitter."""
+  w = np.exp(log_w - np.max(log_w))
+  w = w / w.sum()
+  cdf = np.concatenate([[0.], np.minimum(1., np.cumsum(w[:-1])), [1.]])
+  u = np.linspace(0, 1. - _F32_EPS, n)
+  last = len(cdf) - 1
+  below = np.searchsorted(cdf, u, side='right') - 1             # the last knot with cdf <= u
+  i0, i1 = np.clip(below, 0, last), np.clip(below + 1, 0, last)
+  with np.errstate(divide='ignore', invalid='ignore'):
+    frac = np.clip(np.nan_to_num((u - cdf[i0]) / (cdf[i1] - cdf[i0]), nan=0.), 0, 1)
+  return t[i0] + frac * (t[i1] - t[i0])
+
+
+def generate_ellipse_path(poses, n_frames=120, const_speed=True, z_variation=0., z_phase=0.):
+  """An elliptical path around the captures' focus point (camera_utils.py:230-278): axes at the 90th percentile of the
+  camera offsets, at height z = 0 (or, with z_variation, swinging between the 10th and 90th percentile of the capture
+  heights); with const_speed the angles are resampled so that equal steps cover equal arc length."""
+  center = focus_point_fn(poses)
+  offset = np.array([center[0], center[1], 0])
+  sc = np.percentile(np.abs(poses[:, :3, 3] - offset), 90, axis=0)
+  low, high = -sc + offset, sc + offset
+  z_low = np.percentile(poses[:, :3, 3], 10, axis=0)
+  z_high = np.percentile(poses[:, :3, 3], 90, axis=0)
+
+  def get_positions(theta):
+    return np.stack([
+        low[0] + (high - low)[0] * (np.cos(theta) * .5 + .5),
+        low[1] + (high - low)[1] * (np.sin(theta) * .5 + .5),
+        z_variation * (z_low[2] + (z_high - z_low)[2] * (np.cos(theta + 2 * np.pi * z_phase) * .5 + .5)),
+    ], -1)
+
+  theta = np.linspace(0, 2. * np.pi, n_frames + 1, endpoint=True)
+  positions = get_positions(theta)
+  if const_speed:
+    lengths = np.linalg.norm(positions[1:] - positions[:-1], axis=-1)
+    theta = _invert_step_cdf(theta, np.log(lengths), n_frames + 1)
+    positions = get_positions(theta)
+  positions = positions[:-1]                                    # the last one repeats the first
+  avg_up = poses[:, :3, 1].mean(0)
+  avg_up = avg_up / np.linalg.norm(avg_up)
+  ind_up = np.argmax(np.abs(avg_up))
+  up = np.eye(3)[ind_up] * np.sign(avg_up[ind_up])              # the world axis closest to the mean up vector
+  return np.stack([viewmatrix(p - center, up, p) for p in positions])
+
+
+def generate_interpolated_path(poses, n_interp, spline_degree=5, smoothness=.03, rot_weight=.1):
+  """A smooth B-spline through keyframe poses (camera_utils.py:281-328): every pose becomes three points (position, a point
+  rot_weight along the view axis, a point rot_weight along up), one spline goes through the nine coordinates, and the
+  n_interp * (n - 1) samples are turned back into poses.  The degree falls back to n - 1 for few keyframes."""
+  import scipy.interpolate
+  pos = poses[:, :3, -1]
+  points = np.stack([pos, pos - rot_weight * poses[:, :3, 2], pos + rot_weight * poses[:, :3, 1]], 1)
+  n_key = points.shape[0]
+  n = n_interp * (n_key - 1)
+  tck, _ = scipy.interpolate.splprep(points.reshape(n_key, -1).T, k=min(spline_degree, n_key - 1), s=smoothness)
+  new_points = np.array(scipy.interpolate.splev(np.linspace(0, 1, n, endpoint=False), tck)).T.reshape(n, 3, 3)
+  return np.array([viewmatrix(p - l, u - p, p) for p, l, u in new_points])
+
+
+def interpolate_1d(x, n_interp, spline_degree, smoothness):
+  """camera_utils.py:331-340: a smoothing spline through a 1-D signal, sampled n_interp times per interval."""
+  import scipy.interpolate
+  tck = scipy.interpolate.splrep(np.linspace(0, 1, len(x), endpoint=True), x, s=smoothness, k=spline_degree)
+  return scipy.interpolate.splev(np.linspace(0, 1, n_interp * (len(x) - 1), endpoint=False), tck)
+
+
+def create_render_spline_path(config, image_names, poses, exposures):
+  """camera_utils.py:343-395: the spline path through the poses of the images named by Config.render_spline_keyframes (a
+  directory of images, or a text file with one name per line).  Returns (keyframe indices, render poses, render exposures
+  or None)."""
+  import os
+  if os.path.isdir(config.render_spline_keyframes):
+    keyframe_names = sorted(os.listdir(config.render_spline_keyframes))
+  else:
+    with open(config.render_spline_keyframes, 'r', encoding='utf-8') as fp:
+      keyframe_names = fp.read().splitlines()
+  spline_indices = np.array([i for i, n in enumerate(image_names) if n in keyframe_names])
+  render_poses = generate_interpolated_path(poses[spline_indices], n_interp=config.render_spline_n_interp,
+                                            spline_degree=config.render_spline_degree,
+                                            smoothness=config.render_spline_smoothness, rot_weight=.1)
+  render_exposures = None
+  if config.render_spline_interpolate_exposure:
+    if exposures is None:
+      raise ValueError('config.render_spline_interpolate_exposure is True but create_render_spline_path() was passed '
+                       'exposures=None.')
+    # (heavy smoothing: a flickering exposure is worse than a lagging one)
+    log_exposure = interpolate_1d(np.log(exposures[spline_indices]), config.render_spline_n_interp, spline_degree=5, smoothness=20)
+    render_exposures = np.exp(log_exposure)
+  return spline_indices, render_poses, render_exposures

@@ -164,3 +164,58 @@ extern "C" int mnr_pixels_to_rays(int64_t B, const int32_t* pix_x_int, const int
   MNR_CHECK_LAUNCH();
   return MNR_OK;
 }
+
+// Spherical camera (camera_utils.py:716-764).  |dx| is a difference of nearby unit vectors: in float32 it would lose
+// log10(W / 6) digits, so the three grid directions are formed in float64 and every output is rounded once.
+__device__ __forceinline__ void sph_direction(const double R[9], int h, int w, int H, int W, double d[3]) {
+  const double two_pi = 6.283185307179586476925286766559, pi = 3.141592653589793238462643383279;
+  const double theta = w == W ? two_pi : (double)w * (two_pi / (double)W);       // np.linspace: i * step, the end point exact
+  const double phi = h == H ? pi : (double)h * (pi / (double)H);
+  const double c[3] = {-sin(phi) * sin(theta), cos(phi), sin(phi) * cos(theta)};
+#pragma unroll
+  for (int i = 0; i < 3; ++i) d[i] = R[i * 3 + 0] * c[0] + R[i * 3 + 1] * c[1] + R[i * 3 + 2] * c[2];
+}
+
+__global__ void spherical_rays_kernel(int H, int W, const float* __restrict__ camtoworld, float* __restrict__ origins,
+                                      float* __restrict__ directions, float* __restrict__ viewdirs, float* __restrict__ radii,
+                                      float* __restrict__ imageplane) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= (int64_t)H * W) return;
+  const int h = (int)(b / W), w = (int)(b - (int64_t)h * W);
+  double R[9];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R[i * 3 + j] = (double)camtoworld[i * 4 + j];
+  }
+  double d[3], dx[3], dy[3];
+  sph_direction(R, h, w, H, W, d);
+  sph_direction(R, h, w + 1, H, W, dx);
+  sph_direction(R, h + 1, w, H, W, dy);
+  double sx = 0.0, sy = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double ex = dx[i] - d[i], ey = dy[i] - d[i];
+    sx += ex * ex;
+    sy += ey * ey;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    origins[b * 3 + i] = camtoworld[i * 4 + 3];
+    directions[b * 3 + i] = (float)d[i];
+    viewdirs[b * 3 + i] = (float)d[i];
+  }
+  radii[b] = (float)((0.5 * (sqrt(sx) + sqrt(sy))) * 2.0 / sqrt(12.0));
+  imageplane[b * 2 + 0] = 0.0f;
+  imageplane[b * 2 + 1] = 0.0f;
+}
+
+extern "C" int mnr_spherical_rays(int H, int W, const float* camtoworld, float* origins, float* directions, float* viewdirs,
+                                  float* radii, float* imageplane, void* stream) {
+  MNR_CHECK_ARG(H > 0 && W > 0 && (int64_t)H * W * 3 < (1ll << 31), "mnr_spherical_rays: bad image shape [%d, %d]", H, W);
+  MNR_CHECK_ARG(camtoworld && origins && directions && viewdirs && radii && imageplane, "mnr_spherical_rays: null argument");
+  hipLaunchKernelGGL(spherical_rays_kernel, dim3(mnr_cdiv((int64_t)H * W, 256)), dim3(256), 0, (hipStream_t)stream, H, W, camtoworld,
+                     origins, directions, viewdirs, radii, imageplane);
+  MNR_CHECK_LAUNCH();
+  return MNR_OK;
+}

@@ -8,8 +8,14 @@ gather, and rays come from `camera_utils.cast_ray_batch` (csrc/camera.hip) -- ei
 (an analytic scene for offline runs; tests/helpers.py uses the same scene) and 'llff' (COLMAP `sparse/0` binaries or
 NGP `transforms.json` poses; forward-facing NDC and 360 scenes, datasets.py:563-712).  RawNeRF / DTU / TAT loaders need
 rawpy or dataset-specific files that cannot be exercised here and are not restated.
+
+With `Config.render_path` the cameras of the 'test' split are a render path instead of the held-out views (datasets.py:297-314):
+a spiral (forward-facing), an ellipse or a spline through keyframes for 'llff', an ellipse over its own test cameras for
+'procedural', or the poses of `Config.render_path_file`; batches then carry rays only.  `Config.render_camtype = 'pano'`
+renders a spherical camera (camera_utils.cast_spherical_rays).
 """
 
+import dataclasses
 import json
 import os
 
@@ -38,6 +44,9 @@ class Dataset:
     self._num_border_pixels_to_mask = config.num_border_pixels_to_mask
     self._cast_rays_in_train_step = config.cast_rays_in_train_step
     self._test_camera_idx = 0
+    self.render_path = config.render_path
+    self._render_spherical = False
+    self.render_exposures = None
     self.near, self.far = config.near, config.far
     self.distortion_params = None
     self.pixtocam_ndc = None
@@ -47,6 +56,21 @@ class Dataset:
     self.height = self.width = self.focal = None
     self._gen = torch.Generator(device=self.device).manual_seed(20200823 + seed)
     self._load_renderings(config)
+    if self.render_path:                                # datasets.py:297-314
+      if config.render_path_file is not None:
+        with open(config.render_path_file, 'rb') as fp:
+          self.camtoworlds = np.load(fp)
+      if config.render_resolution is not None:
+        self.width, self.height = (int(v) for v in config.render_resolution)
+      if config.render_focal is not None:
+        self.focal = config.render_focal
+      if config.render_camtype is not None:
+        if config.render_camtype == 'pano':
+          self._render_spherical = True
+        else:
+          self.camtype = camera_utils.ProjectionType(config.render_camtype)
+      self.distortion_params = None
+      self.pixtocams = camera_utils.get_pixtocam(self.focal, self.width, self.height).numpy()
     to = lambda a, dt=torch.float32: None if a is None else torch.as_tensor(np.asarray(a)).to(self.device, dt)
     self.images = to(self.images)
     self.disp_images, self.normal_images, self.alphas = to(self.disp_images), to(self.normal_images), to(self.alphas)
@@ -84,12 +108,16 @@ class Dataset:
     pixels = utils.Pixels(pix_x_int=pix_x_int, pix_y_int=pix_y_int,
                           lossmult=bs(1.) if lossmult is None else lossmult, near=bs(self.near), far=bs(self.far),
                           cam_idx=bs(cam_idx, torch.int32))
+    if self.render_path and self.render_exposures is not None:      # datasets.py:426-428
+      pixels = dataclasses.replace(pixels, exposure_values=bs(float(self.render_exposures[int(cam_idx)])))
     if self._cast_rays_in_train_step and self.split == 'train':
       rays = pixels
     else:
       rays = camera_utils.cast_ray_batch(self.cameras, pixels, self.camtype)
     ci = torch.as_tensor(cam_idx, device=self.device).expand(shape).long()
-    batch = dict(rays=rays, rgb=self.images[ci, pix_y_int, pix_x_int])
+    batch = dict(rays=rays)
+    if not self.render_path:                            # datasets.py:442
+      batch['rgb'] = self.images[ci, pix_y_int, pix_x_int]
     if self._load_disps:
       batch['disps'] = self.disp_images[ci, pix_y_int, pix_x_int]
     if self._load_normals:
@@ -116,6 +144,9 @@ class Dataset:
 
   def generate_ray_batch(self, cam_idx):
     """datasets.py:490-502: all pixels of one camera, shaped [H, W, ...]."""
+    if self._render_spherical:
+      rays = camera_utils.cast_spherical_rays(self.camtoworlds[int(cam_idx)], self.height, self.width, self.near, self.far)
+      return utils.Batch(rays=rays)
     px, py = camera_utils.pixel_coordinates(self.width, self.height, self.device)
     return self._make_ray_batch(px, py, int(cam_idx))
 
@@ -206,6 +237,9 @@ class Procedural(Dataset):
       self.normal_images, self.alphas = np.stack(nrms, 0), np.stack(alphas, 0)
     self.height, self.width, self.focal = H, W, focal
     self.camtoworlds = c2w
+    if config.render_path:                              # (ours: lets render.py run with no dataset on disk)
+      self.camtoworlds = camera_utils.generate_ellipse_path(c2w, n_frames=config.render_path_frames,
+                                                            z_variation=config.z_variation, z_phase=config.z_phase)
     self.pixtocams = camera_utils.get_pixtocam(focal, W, H).numpy()
 
 
@@ -314,14 +348,13 @@ def load_blender_posedata(data_dir, split=None):
 class LLFF(Dataset):
   """datasets.py:563-712 for ordinary (non-raw) captures: COLMAP `sparse/0` or NGP `transforms.json` poses, images in
   `images[_factor]`, forward-facing scenes in NDC (recenter + bound rescale) or 360 scenes (PCA alignment into the unit
-  cube), every `llffhold`-th image held out.  Render paths (spiral / ellipse / spline) and RawNeRF inputs are not restated."""
+  cube), every `llffhold`-th image held out; with Config.render_path the cameras are the spiral (forward-facing), the spline
+  through Config.render_spline_keyframes, or the ellipse path.  RawNeRF inputs are not restated."""
 
   def _load_renderings(self, config):
     from PIL import Image
     if config.rawnerf_mode:
       raise NotImplementedError('RawNeRF inputs need rawpy (raw_utils.load_raw_dataset)')
-    if config.render_path:
-      raise NotImplementedError('render paths are out of scope (DESIGN.md section 7)')
     factor = config.factor if config.factor > 0 else 1
     suffix = f'_{config.factor}' if config.factor > 0 else ''
     colmap_dir = os.path.join(self.data_dir, 'sparse/0/')
@@ -353,17 +386,26 @@ class LLFF(Dataset):
       scale = 1. / (bounds.min() * .75)
       poses[:, :3, 3] *= scale
       self.colmap_to_world_transform = np.diag([scale] * 3 + [1])
+      bounds = bounds * scale
       poses, transform = camera_utils.recenter_poses(poses)
       self.colmap_to_world_transform = transform @ self.colmap_to_world_transform
+      if config.render_path:                            # datasets.py:665-667
+        self.render_poses = camera_utils.generate_spiral_path(poses, bounds, n_frames=config.render_path_frames)
     else:
       poses, transform = camera_utils.transform_poses_pca(poses)
       self.colmap_to_world_transform = transform
+      if config.render_path and config.render_spline_keyframes is not None:      # datasets.py:672-682
+        self.spline_indices, self.render_poses, self.render_exposures = camera_utils.create_render_spline_path(
+            config, image_names, poses, None)
+      elif config.render_path:
+        self.render_poses = camera_utils.generate_ellipse_path(poses, n_frames=config.render_path_frames,
+                                                               z_variation=config.z_variation, z_phase=config.z_phase)
     self.poses = poses
     all_indices = np.arange(images.shape[0])
     train_indices = all_indices if config.llff_use_all_images_for_training else all_indices % config.llffhold != 0
     indices = {'test': all_indices[all_indices % config.llffhold == 0], 'train': train_indices}[self.split]
     self.images = images[indices]
-    self.camtoworlds = poses[indices]
+    self.camtoworlds = self.render_poses if config.render_path else poses[indices]
     self.height, self.width = self.images.shape[1:3]
 
 

@@ -1142,6 +1142,129 @@ def cc_apply(img, warp, out=None):
   return out
 
 
+# ----------------------------------------------------------------------------- visualisation (csrc/vis.hip, csrc/camera.hip)
+
+
+def spherical_rays(camtoworld, height, width):
+  """camera_utils.cast_spherical_rays' arrays (camera_utils.py:716-764) for one [3,4] camera: (origins, directions, viewdirs
+  [H,W,3], radii [H,W,1], imageplane [H,W,2]), float32 on the device of `camtoworld`."""
+  if not _on_device(camtoworld):
+    raise ValueError('spherical_rays: camtoworld must be a device tensor (the HIP path has no CPU fallback)')
+  c2w = camtoworld[..., :3, :4].to(f32).reshape(3, 4).contiguous()
+  H, W = int(height), int(width)
+  new = lambda c: torch.empty((H, W, c), dtype=f32, device=c2w.device)
+  origins, directions, viewdirs, radii, imageplane = new(3), new(3), new(3), new(1), new(2)
+  L.check(lib().mnr_spherical_rays(H, W, _ptr(c2w), _ptr(origins), _ptr(directions), _ptr(viewdirs), _ptr(radii), _ptr(imageplane),
+                                   _stream()))
+  return origins, directions, viewdirs, radii, imageplane
+
+
+def weighted_percentile(x, w, ps, assume_sorted=False, out=None):
+  """vis.weighted_percentile (vis.py:22-30): the weighted percentiles `ps` (1 to 4 numbers in [0, 100]) of the values x with
+  weights w, both flattened, as a float32 device tensor [len(ps)]; nothing is read back.  The order comes from a stable
+  torch.sort; the weight of the i-th sorted value is w[min(order[i], w.numel() - 1)] (a clamping gather, as jax documents)."""
+  _chk(x, f32, 'x')
+  _chk(w, f32, 'w')
+  _chk(out, f32, 'out', allow_none=True)
+  ps = [float(p) for p in (ps if hasattr(ps, '__len__') else [ps])]
+  if not 1 <= len(ps) <= L.VIS_MAX_PERCENTILES:
+    raise ValueError(f'weighted_percentile: {len(ps)} percentiles, 1 to {L.VIS_MAX_PERCENTILES} are taken at once')
+  x = x.reshape(-1)
+  N, NW = x.numel(), w.numel()
+  if assume_sorted:
+    xs, order = x, torch.arange(N, dtype=torch.int64, device=x.device)
+  else:
+    xs, order = torch.sort(x, stable=True)
+  partials = torch.empty((max(lib().mnr_weighted_percentile_partials(N), 1),), dtype=f64, device=x.device)
+  if out is None:
+    out = torch.empty((len(ps),), dtype=f32, device=x.device)
+  L.check(lib().mnr_weighted_percentile(N, _ptr(xs), _ptr(order), NW, _ptr(w), len(ps), (C.c_double * len(ps))(*ps), _ptr(partials),
+                                        _ptr(out), _stream()))
+  return out
+
+
+def vis_cmap(value, lohi, *, curve=None, modulus=None, lut=None, acc=None, dark=0.8, light=1.0, width=8, out=None, out_u8=None,
+             want_f32=True):
+  """The per-pixel part of vis.visualize_cmap (vis.py:85-106): value [H,W] or [H,W,1] with a LUT [n,3], [H,W,3] without;
+  lohi a float32 device pair (lo, hi) before the curve (None with a modulus); curve None / 'log' / 'neg_log'
+  (+-log(x + eps32)) / 'ln' (log(x)); acc [H,W]: matte the result over the checker.  Returns the [H,W,3] float32 image; with out_u8 (a
+  [H,W,3] uint8 device tensor) also trunc(clip(., 0, 1) 255) there (want_f32=False: only that, and it is returned)."""
+  _chk(value, f32, 'value')
+  _chk(lohi, f32, 'lohi', allow_none=True)
+  _chk(lut, f32, 'lut', allow_none=True)
+  _chk(acc, f32, 'acc', allow_none=True)
+  _chk(out, f32, 'out', allow_none=True)
+  _chk(out_u8, torch.uint8, 'out_u8', allow_none=True)
+  if value.dim() == 2:
+    value = value[..., None]
+  if value.dim() != 3:
+    raise ValueError(f'vis_cmap: value must be [H,W] or [H,W,C], is {tuple(value.shape)}')
+  H, W, Cn = (int(v) for v in value.shape)
+  if lut is not None and (lut.dim() != 2 or lut.shape[1] != 3):
+    raise ValueError(f'vis_cmap: the LUT must be [n,3], is {tuple(lut.shape)}')
+  if lohi is not None and lohi.numel() != 2:
+    raise ValueError('vis_cmap: lohi must hold two values')
+  if acc is not None and tuple(acc.shape) != (H, W):
+    raise ValueError(f'vis_cmap: acc {tuple(acc.shape)} must be [{H},{W}]')
+  if curve not in L.VIS_CURVE:
+    raise ValueError(f'vis_cmap: unknown curve {curve!r}')
+  if out is None and (want_f32 or out_u8 is None):
+    out = torch.empty((H, W, 3), dtype=f32, device=value.device)
+  for o in (out, out_u8):
+    if o is not None and tuple(o.shape) != (H, W, 3):
+      raise ValueError(f'vis_cmap: an output of shape {tuple(o.shape)} must be [{H},{W},3]')
+  a = L.VisCmapArgs()
+  a.H, a.W, a.C, a.curve, a.modulus = H, W, Cn, L.VIS_CURVE[curve], float(modulus) if modulus else 0.0
+  a.value, a.lohi = value.data_ptr(), None if lohi is None else lohi.data_ptr()
+  a.lut, a.n_lut = (None, 0) if lut is None else (lut.data_ptr(), int(lut.shape[0]))
+  a.acc, a.dark, a.light, a.width = None if acc is None else acc.data_ptr(), float(dark), float(light), int(width)
+  a.out, a.out_u8 = None if out is None else out.data_ptr(), None if out_u8 is None else out_u8.data_ptr()
+  L.check(lib().mnr_vis_cmap(C.byref(a), _stream()))
+  return out if out is not None else out_u8
+
+
+def vis_matte(x, acc, *, preop=None, origins=None, directions=None, distance=None, dark=0.8, light=1.0, width=8, out=None):
+  """vis.matte (vis.py:39-45) of pre(x) [H,W,C] over the checker with acc [H,W].  preop None, 'half' (x / 2 + 0.5), 'tanh',
+  or 'coord_mod' (x is None: ((origins + directions distance + 1) mod 2) / 2, vis.py:109-111,185; without directions and
+  distance the origins are the coordinates)."""
+  if preop not in L.VIS_PREOP:
+    raise ValueError(f'vis_matte: unknown pre-op {preop!r}')
+  _chk(acc, f32, 'acc')
+  H, W = (int(v) for v in acc.shape)
+  a = L.VisMatteArgs()
+  if preop == 'coord_mod':
+    if (directions is None) != (distance is None):
+      raise ValueError('vis_matte: directions and distance go together')
+    for t, nm in ((origins, 'origins'), (directions, 'directions')):
+      _chk(t, f32, nm, allow_none=nm == 'directions')
+      if t is not None and tuple(t.shape) != (H, W, 3):
+        raise ValueError(f'vis_matte: {nm} {tuple(t.shape)} must be [{H},{W},3]')
+    _chk(distance, f32, 'distance', allow_none=True)
+    if distance is not None and tuple(distance.shape) != (H, W):
+      raise ValueError(f'vis_matte: distance {tuple(distance.shape)} must be [{H},{W}]')
+    Cn = 3
+    a.origins = origins.data_ptr()
+    if directions is not None:
+      a.directions, a.distance = directions.data_ptr(), distance.data_ptr()
+  else:
+    _chk(x, f32, 'x')
+    if x.dim() == 2:
+      x = x[..., None]
+    if x.dim() != 3 or tuple(x.shape[:2]) != (H, W):
+      raise ValueError(f'vis_matte: x {tuple(x.shape)} must be [{H},{W},C]')
+    Cn = int(x.shape[2])
+    a.x = x.data_ptr()
+  _chk(out, f32, 'out', allow_none=True)
+  if out is None:
+    out = torch.empty((H, W, Cn), dtype=f32, device=acc.device)
+  elif tuple(out.shape) != (H, W, Cn):
+    raise ValueError(f'vis_matte: out {tuple(out.shape)} must be [{H},{W},{Cn}]')
+  a.H, a.W, a.C, a.preop = H, W, Cn, L.VIS_PREOP[preop]
+  a.acc, a.dark, a.light, a.width, a.out = acc.data_ptr(), float(dark), float(light), int(width), out.data_ptr()
+  L.check(lib().mnr_vis_matte(C.byref(a), _stream()))
+  return out
+
+
 def interlevel_loss(mult, t, w, t_env, w_env, stats, g_w_env, *, B_valid):
   for x, nm in ((t, 't'), (w, 'w'), (t_env, 't_env'), (w_env, 'w_env')):
     _chk(x, f32, nm)
