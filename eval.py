@@ -37,10 +37,11 @@ def main():
   torch.cuda.set_device(dev)
   config = configs.load_preset(args.preset, args.gin_bindings) if args.preset else \
       configs.load_config(args.gin_configs, args.gin_bindings, save_config=False)
-  if config.eval_raw_affine_cc:
-    raise SystemExit('eval.py: Config.eval_raw_affine_cc = True is not supported (raw_utils.match_images_affine needs the '
-                     'DNG metadata of the RawNeRF loader); the quadratic image.color_correct is used otherwise')
+  if config.eval_raw_affine_cc and not config.rawnerf_mode:
+    raise SystemExit('eval.py: Config.eval_raw_affine_cc = True needs Config.rawnerf_mode (raw_utils.match_images_affine is '
+                     'meant for the raw test scenes); the quadratic image.color_correct is used otherwise')
   dataset = datasets.load_dataset('test', config.data_dir, config, device=dev)
+  postprocess_fn = dataset.metadata['postprocess_fn'] if config.rawnerf_mode else None          # eval.py:57-60
   model, state, render_eval_pfn, _, _ = train_utils.setup_model(config, 20200823, dataset=dataset, device=dev)
   if not config.checkpoint_dir or not os.path.isdir(config.checkpoint_dir):
     raise SystemExit(f'eval.py: Config.checkpoint_dir = {config.checkpoint_dir!r} is not a directory')
@@ -76,12 +77,14 @@ def main():
     if rank != 0:
       continue
     render_times.append(time.time() - t0)
-    mse = float(((rendering['rgb'] - batch.rgb)**2).mean())
+    pp = postprocess_fn if postprocess_fn is not None else (lambda z: z)
+    mse = float(((pp(rendering['rgb']) - pp(batch.rgb))**2).mean())
     psnr = -10. / math.log(10.) * math.log(max(mse, 1e-30))
     psnrs.append(psnr)
     print(f'Eval image {idx + 1}/{n}: {time.time() - t0:.3f}s, psnr {psnr:.3f}', flush=True)
     t1 = time.time()
-    metric, metric_cc, images = image.evaluate_image(rendering, batch, config, metric_harness)    # eval.py:118-163
+    metric, metric_cc, images = image.evaluate_image(rendering, batch, config, metric_harness,
+                                                     postprocess_fn=postprocess_fn)               # eval.py:118-163
     print(f'Color corrected and scored in {time.time() - t1:0.3f}s')
     for m, v in metric.items():
       print(f'{m:30s} = {v:.4f}')

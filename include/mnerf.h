@@ -797,6 +797,55 @@ typedef struct {
 } mnr_vis_matte_args;
 int mnr_vis_matte(const mnr_vis_matte_args* args, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * RawNeRF data path  (the per-pixel work of internal/raw_utils.py; csrc/raw.hip)
+ * Deterministic: float64 sums are per-workgroup partials added in a fixed order, counts are integer atomics.
+ * ------------------------------------------------------------------------- */
+typedef enum { MNR_RAW_U16 = 0, MNR_RAW_F32 = 1 } mnr_raw_dtype;
+
+/* raw_utils.load_raw_dataset:354-382 for a stack of Bayer mosaics [N,H,W] (RGGB, red at (0,0); H, W even; dtype a
+ * mnr_raw_dtype): v = (raw - black[i]) / (white[i] - black[i]) * scale in float64, rounded once to float32 (black, white:
+ * DEVICE [N] float64, both NULL: v = raw); raw_utils.bilinear_demosaic in float32, with the wrap-around of its np.roll at
+ * the borders; n_downsample > 1 (must divide H and W): the area mean over n x n blocks (image.downsample), added in
+ * float64 row by row and rounded once; the full-resolution image is not written.  out [N, H/n, W/n, 3] float32. */
+int mnr_raw_demosaic(int N, int H, int W, int dtype, const void* mosaic, const double* black, const double* white,
+                     double scale, int n_downsample, float* out, void* stream);
+
+/* raw_utils.postprocess_raw in float64: rgb_lin = raw camtorgb^T; linear_only != 0: out_f64 = rgb_lin and nothing else
+ * (what the exposure percentile is taken of).  Otherwise srgb = image.linear_to_srgb(clip(rgb_lin / exposure, 0, 1)), with
+ * exposure = *exposure_dev when that is given (a device scalar: an auto-exposure needs no host read), else `exposure`.
+ * Any subset of the outputs: out_f64, out_f32 (rounded once), out_u8 = trunc(clip(nan_to_num(srgb), 0, 1) 255)
+ * (utils.save_img_u8). */
+typedef struct {
+  int64_t P;
+  const void* raw;                 /* [P,3] float32, or float64 when raw_f64 is set */
+  int raw_f64;
+  double camtorgb[9];              /* row-major [3,3] */
+  double exposure;
+  const double* exposure_dev;      /* device [1] or NULL */
+  int linear_only;
+  double* out_f64;                 /* [P,3] or NULL */
+  float* out_f32;                  /* [P,3] or NULL */
+  unsigned char* out_u8;           /* [P,3] or NULL */
+} mnr_raw_post_args;
+int mnr_raw_postprocess(const mnr_raw_post_args* args, void* stream);
+
+/* np.percentile(x[0:N], p) of float64 values, 0 <= p <= 100: the exact order statistics a, b at floor and ceil of
+ * p / 100 (M - 1) over the M finite values (non-finite ones are ignored; *out = NaN when there is none), combined as numpy's
+ * _lerp does: a + (b - a) t, or b - (b - a)(1 - t) for t >= 0.5.  Radix select on the 64-bit patterns, 8 bits a pass, over
+ * many workgroups: per-workgroup LDS histograms merged by integer atomics.  workspace: mnr_quantile_f64_workspace(N)
+ * bytes of device memory (0: N is not valid), overwritten.  out: device [1]. */
+int64_t mnr_quantile_f64_workspace(int64_t N);
+int mnr_quantile_f64(int64_t N, const double* x, double p, void* workspace, double* out, void* stream);
+
+/* raw_utils.best_fit_affine's sums for axis = (0, 1): from est, gt [P,3] float64, out [4][3] float64 = per channel the sums
+ * of gt, est, gt est, gt gt.  partials: workspace of mnr_affine_sums_partials(P) doubles. */
+int mnr_affine_sums_partials(int64_t P);
+int mnr_affine_sums(int64_t P, const double* est, const double* gt, double* partials, double* out, void* stream);
+
+/* raw_utils.match_images_affine's last line: out[i, c] = (est[i, c] - b[c]) / a[c]; a, b: HOST [3]; out may alias est. */
+int mnr_affine_apply(int64_t P, const double* est, const double* a, const double* b, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

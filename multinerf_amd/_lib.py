@@ -191,6 +191,14 @@ class VisMatteArgs(C.Structure):
               ('directions', vp), ('distance', vp), ('dark', C.c_float), ('light', C.c_float), ('width', C.c_int), ('out', vp)]
 
 
+RAW_DTYPE = {'uint16': 0, 'float32': 1}      # mnr_raw_dtype
+
+
+class RawPostArgs(C.Structure):
+  _fields_ = [('P', C.c_int64), ('raw', vp), ('raw_f64', C.c_int), ('camtorgb', C.c_double * 9), ('exposure', C.c_double),
+              ('exposure_dev', vp), ('linear_only', C.c_int), ('out_f64', vp), ('out_f32', vp), ('out_u8', vp)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
@@ -270,6 +278,13 @@ _PROTOS = {
     'mnr_weighted_percentile': ([i64, vp, vp, i64, vp, i32, C.POINTER(C.c_double), vp, vp, vp], i32),
     'mnr_vis_cmap': ([C.POINTER(VisCmapArgs), vp], i32),
     'mnr_vis_matte': ([C.POINTER(VisMatteArgs), vp], i32),
+    'mnr_raw_demosaic': ([i32, i32, i32, i32, vp, vp, vp, C.c_double, i32, vp, vp], i32),
+    'mnr_raw_postprocess': ([C.POINTER(RawPostArgs), vp], i32),
+    'mnr_quantile_f64_workspace': ([i64], i64),
+    'mnr_quantile_f64': ([i64, vp, C.c_double, vp, vp, vp], i32),
+    'mnr_affine_sums_partials': ([i64], i32),
+    'mnr_affine_sums': ([i64, vp, vp, vp, vp, vp], i32),
+    'mnr_affine_apply': ([i64, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

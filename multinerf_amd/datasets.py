@@ -6,8 +6,15 @@ gather, and rays come from `camera_utils.cast_ray_batch` (csrc/camera.hip) -- ei
 `Config.cast_rays_in_train_step`, inside the train step exactly like the reference's fast path
 (datasets.py:431-433).  Loaders: 'blender' (transforms_*.json + PNG, datasets.py:507-560) and 'procedural'
 (an analytic scene for offline runs; tests/helpers.py uses the same scene) and 'llff' (COLMAP `sparse/0` binaries or
-NGP `transforms.json` poses; forward-facing NDC and 360 scenes, datasets.py:563-712).  RawNeRF / DTU / TAT loaders need
-rawpy or dataset-specific files that cannot be exercised here and are not restated.
+NGP `transforms.json` poses; forward-facing NDC and 360 scenes, datasets.py:563-712).  DTU / TAT loaders need
+dataset-specific files that cannot be exercised here and are not restated.
+
+With `Config.rawnerf_mode` the 'llff' loader reads a raw capture through `raw_utils.load_raw_dataset` (`raw/*.dng` with
+rawpy, or `raw/*.npy` mosaics, plus `raw/*.json` EXIF; the `hdrplus_test/merged` test scenes included): the mosaics are
+normalised, demosaicked and downsampled on the device (csrc/raw.hip), `metadata` carries the exposure indices and values that
+every ray batch then holds, and `Config.apply_bayer_mask` makes the train batches' `lossmult` the Bayer mask.  The
+'procedural' loader synthesises such a capture from its analytic scene.  Exposures from JPEG EXIF (`use_exif`,
+`self.exposures`) are not restated.
 
 With `Config.render_path` the cameras of the 'test' split are a render path instead of the held-out views (datasets.py:297-314):
 a spiral (forward-facing), an ellipse or a spline through keyframes for 'llff', an ellipse over its own test cameras for
@@ -47,6 +54,9 @@ class Dataset:
     self.render_path = config.render_path
     self._render_spherical = False
     self.render_exposures = None
+    self.metadata = None                                # datasets.py:283: the raw loader's dict (exposure_idx, exposure_values, ...)
+    self.exposures = None                               # (JPEG EXIF exposures: not restated, always None)
+    self._apply_bayer_mask = config.apply_bayer_mask
     self.near, self.far = config.near, config.far
     self.distortion_params = None
     self.pixtocam_ndc = None
@@ -71,7 +81,12 @@ class Dataset:
           self.camtype = camera_utils.ProjectionType(config.render_camtype)
       self.distortion_params = None
       self.pixtocams = camera_utils.get_pixtocam(self.focal, self.width, self.height).numpy()
-    to = lambda a, dt=torch.float32: None if a is None else torch.as_tensor(np.asarray(a)).to(self.device, dt)
+    to = lambda a, dt=torch.float32: None if a is None else \
+        (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))).to(self.device, dt)
+    self._exposure_idx = self._exposure_values = None
+    if self.metadata is not None:
+      self._exposure_idx = to(self.metadata['exposure_idx'], torch.int32)
+      self._exposure_values = to(self.metadata['exposure_values'])
     self.images = to(self.images)
     self.disp_images, self.normal_images, self.alphas = to(self.disp_images), to(self.normal_images), to(self.alphas)
     self.camtoworlds = to(self.camtoworlds)[..., :3, :4].contiguous()
@@ -108,6 +123,10 @@ class Dataset:
     pixels = utils.Pixels(pix_x_int=pix_x_int, pix_y_int=pix_y_int,
                           lossmult=bs(1.) if lossmult is None else lossmult, near=bs(self.near), far=bs(self.far),
                           cam_idx=bs(cam_idx, torch.int32))
+    if self.metadata is not None:                       # datasets.py:418-422: exposure index and relative shutter speed
+      idx = torch.as_tensor(0 if self.render_path else cam_idx, device=self.device).long()
+      pixels = dataclasses.replace(pixels, exposure_idx=bs(self._exposure_idx[idx], torch.int32),
+                                   exposure_values=bs(self._exposure_values[idx]))
     if self.render_path and self.render_exposures is not None:      # datasets.py:426-428
       pixels = dataclasses.replace(pixels, exposure_values=bs(float(self.render_exposures[int(cam_idx)])))
     if self._cast_rays_in_train_step and self.split == 'train':
@@ -139,8 +158,12 @@ class Dataset:
       cam = ri(0, self._n_examples, (num_patches, 1, 1)).expand(px.shape)
     else:
       cam = ri(0, self._n_examples, (1,)).expand(px.shape)
-    b = self._make_ray_batch(px.reshape(-1), py.reshape(-1), cam.reshape(-1))
-    return b
+    px, py = px.reshape(-1), py.reshape(-1)
+    lossmult = None
+    if self._apply_bayer_mask:                          # datasets.py:477-479: the Bayer mosaic mask of each pixel
+      from multinerf_amd import raw_utils
+      lossmult = raw_utils.pixels_to_bayer_mask(px, py)
+    return self._make_ray_batch(px, py, cam.reshape(-1), lossmult=lossmult)
 
   def generate_ray_batch(self, cam_idx):
     """datasets.py:490-502: all pixels of one camera, shaped [H, W, ...]."""
@@ -205,7 +228,8 @@ class Procedural(Dataset):
   def _load_renderings(self, config):
     n = self.NUM_TRAIN if self.split == 'train' else self.NUM_TEST
     rs = np.random.default_rng(7 if self.split == 'train' else 8)
-    H = W = self.SIZE // max(config.factor, 1)
+    raw = bool(config.rawnerf_mode)
+    H = W = self.SIZE if raw else self.SIZE // max(config.factor, 1)   # (a raw capture is synthesised at full size)
     focal = 1.2 * W
     z = rs.uniform(0.1, 0.9, n)
     phi = rs.uniform(0, 2 * np.pi, n)
@@ -235,6 +259,18 @@ class Procedural(Dataset):
     self.images = np.stack(imgs, 0)
     if self._load_normals:
       self.normal_images, self.alphas = np.stack(nrms, 0), np.stack(alphas, 0)
+    if raw:
+      # the scene as a raw capture, through the processing of raw_utils.load_raw_dataset; the train split stays at
+      # full resolution (datasets.py:570-577)
+      from multinerf_amd import raw_utils
+      if self._load_normals:
+        raise ValueError('compute_normal_metrics is not available for the procedural raw capture')
+      n_down = max(config.factor, 1) if self.split == 'test' else 1
+      mosaics, exifs = raw_utils.synthesize_raw_capture(self.images, self.split, seed=0)
+      self.raw_mosaics = mosaics                        # (host uint16: what a camera would have written)
+      self.images, self.metadata = raw_utils.process_raw_capture(mosaics, raw_utils.process_exif(exifs), 1., config.exposure_percentile,
+                                                                 n_down, self.device)
+      H, W, focal = H // n_down, W // n_down, focal / n_down
     self.height, self.width, self.focal = H, W, focal
     self.camtoworlds = c2w
     if config.render_path:                              # (ours: lets render.py run with no dataset on disk)
@@ -349,14 +385,16 @@ class LLFF(Dataset):
   """datasets.py:563-712 for ordinary (non-raw) captures: COLMAP `sparse/0` or NGP `transforms.json` poses, images in
   `images[_factor]`, forward-facing scenes in NDC (recenter + bound rescale) or 360 scenes (PCA alignment into the unit
   cube), every `llffhold`-th image held out; with Config.render_path the cameras are the spiral (forward-facing), the spline
-  through Config.render_spline_keyframes, or the ellipse path.  RawNeRF inputs are not restated."""
+  through Config.render_spline_keyframes, or the ellipse path.  With Config.rawnerf_mode the images are a raw capture
+  (raw_utils.load_raw_dataset), the train split at full resolution."""
 
   def _load_renderings(self, config):
     from PIL import Image
-    if config.rawnerf_mode:
-      raise NotImplementedError('RawNeRF inputs need rawpy (raw_utils.load_raw_dataset)')
-    factor = config.factor if config.factor > 0 else 1
-    suffix = f'_{config.factor}' if config.factor > 0 else ''
+    # the downsampling factor, unless loading the train split of a raw dataset: raw is trained at full resolution because
+    # of the Bayer mosaic pattern (datasets.py:570-577)
+    use_factor = config.factor > 0 and not (config.rawnerf_mode and self.split == 'train')
+    factor = config.factor if use_factor else 1
+    suffix = f'_{config.factor}' if use_factor else ''
     colmap_dir = os.path.join(self.data_dir, 'sparse/0/')
     pose_data = load_colmap_posedata(colmap_dir) if os.path.exists(colmap_dir) else load_blender_posedata(self.data_dir)
     image_names, poses, pixtocam, distortion_params, camtype = pose_data
@@ -369,14 +407,20 @@ class LLFF(Dataset):
     self.focal = 1. / self.pixtocams[0, 0]
     self.distortion_params = distortion_params
     self.camtype = camtype
-    colmap_image_dir = os.path.join(self.data_dir, 'images')
-    image_dir = os.path.join(self.data_dir, 'images' + suffix)
-    for d in (image_dir, colmap_image_dir):
-      if not os.path.exists(d):
-        raise ValueError(f'Image folder {d} does not exist.')
-    colmap_to_image = dict(zip(sorted(os.listdir(colmap_image_dir)), sorted(os.listdir(image_dir))))
-    images = np.stack([np.asarray(Image.open(os.path.join(image_dir, colmap_to_image[f])), dtype=np.float32)[..., :3]
-                       for f in image_names], 0) / 255.
+    raw_testscene = False
+    if config.rawnerf_mode:                             # datasets.py:604-613
+      from multinerf_amd import raw_utils
+      images, self.metadata, raw_testscene = raw_utils.load_raw_dataset(self.split, self.data_dir, image_names,
+                                                                        config.exposure_percentile, factor, self.device)
+    else:
+      colmap_image_dir = os.path.join(self.data_dir, 'images')
+      image_dir = os.path.join(self.data_dir, 'images' + suffix)
+      for d in (image_dir, colmap_image_dir):
+        if not os.path.exists(d):
+          raise ValueError(f'Image folder {d} does not exist.')
+      colmap_to_image = dict(zip(sorted(os.listdir(colmap_image_dir)), sorted(os.listdir(image_dir))))
+      images = np.stack([np.asarray(Image.open(os.path.join(image_dir, colmap_to_image[f])), dtype=np.float32)[..., :3]
+                         for f in image_names], 0) / 255.
     posefile = os.path.join(self.data_dir, 'poses_bounds.npy')
     bounds = np.load(posefile)[:, -2:] if os.path.exists(posefile) else np.array([0.01, 1.])
     self.colmap_to_world_transform = np.eye(4)
@@ -400,11 +444,19 @@ class LLFF(Dataset):
       elif config.render_path:
         self.render_poses = camera_utils.generate_ellipse_path(poses, n_frames=config.render_path_frames,
                                                                z_variation=config.z_variation, z_phase=config.z_phase)
+    if raw_testscene:                                   # datasets.py:684-691: the first COLMAP image has the test image's pose
+      poses = {'test': poses[:1], 'train': poses[1:]}[self.split]
     self.poses = poses
     all_indices = np.arange(images.shape[0])
-    train_indices = all_indices if config.llff_use_all_images_for_training else all_indices % config.llffhold != 0
+    train_indices = all_indices if (config.llff_use_all_images_for_training or raw_testscene) else all_indices % config.llffhold != 0
     indices = {'test': all_indices[all_indices % config.llffhold == 0], 'train': train_indices}[self.split]
-    self.images = images[indices]
+    if config.rawnerf_mode:                             # datasets.py:711-713 (device images: index with a device tensor)
+      for key in ('exposure_idx', 'exposure_values'):
+        self.metadata[key] = self.metadata[key][indices]
+      indices_t = torch.as_tensor(all_indices[indices]).to(images.device)
+      self.images = images[indices_t]
+    else:
+      self.images = images[indices]
     self.camtoworlds = self.render_poses if config.render_path else poses[indices]
     self.height, self.width = self.images.shape[1:3]
 

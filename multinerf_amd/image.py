@@ -140,26 +140,38 @@ def quantize_u8(img):
   return np.clip(np.rint(img.detach().to(torch.float64).cpu().numpy() * 255.0), 0, 255).astype(np.uint8)
 
 
-def evaluate_image(rendering, batch, config, metric_harness=None):
+def evaluate_image(rendering, batch, config, metric_harness=None, postprocess_fn=None):
   """What the reference's eval.py:118-163 does with one rendered test image, in that order: colour-correct the rendering
   against the ground truth in float64, quantise both versions to 8 bits (Config.eval_quantize_metrics), crop the borders
   (Config.eval_crop_borders), PSNR + SSIM of each, then the disparity and normal metrics.
+
+  postprocess_fn (RawNeRF: the dataset's metadata['postprocess_fn']) maps the rendering, its colour-corrected version and
+  the ground truth from raw space to sRGB after the colour correction and before everything else (eval.py:130-132); the
+  `color` / `color_cc` images returned are the post-processed ones.  With it, Config.eval_raw_affine_cc replaces the
+  quadratic colour correction by raw_utils.match_images_affine.
 
   rendering: the dict of models.render_image ([H,W,...] device tensors); batch: the test batch (rgb, and disps / normals /
   alphas where the metrics need them).  Returns (metric, metric_cc, images_to_save); rendering['rgb_cc'] is added as the
   reference does.  images_to_save maps the reference's file stems (color, color_cc, distance_mean, distance_median,
   normals, acc) to device tensors."""
-  if config.eval_raw_affine_cc:
+  if config.eval_raw_affine_cc and postprocess_fn is None:
     raise ValueError('Config.eval_raw_affine_cc = True is not supported: raw_utils.match_images_affine and the raw '
                      'post-processing need the DNG metadata of the RawNeRF loader')
   if metric_harness is None:
     metric_harness = MetricHarness()
   gt_rgb = batch.rgb[..., :3].to(torch.float64)                                      # eval.py:119-120
   rgb = rendering['rgb'].to(torch.float64)
-  rendering['rgb_cc'] = color_correct(rgb, gt_rgb)                                   # :123
+  if config.eval_raw_affine_cc:                                                      # eval.py:63-66
+    from multinerf_amd import raw_utils
+    rendering['rgb_cc'] = raw_utils.match_images_affine(rgb, gt_rgb)
+  else:
+    rendering['rgb_cc'] = color_correct(rgb, gt_rgb)                                 # :123
+  rgb_cc = rendering['rgb_cc']
+  if postprocess_fn is not None:                                                     # :130-132
+    rgb, rgb_cc, gt_rgb = postprocess_fn(rgb), postprocess_fn(rgb_cc), postprocess_fn(gt_rgb)
   quant, crop = bool(config.eval_quantize_metrics), int(config.eval_crop_borders)
   metric = metric_harness(rgb, gt_rgb, quantize=quant, crop=crop)                    # :134-145
-  metric_cc = metric_harness(rendering['rgb_cc'], gt_rgb, quantize=quant, crop=crop)
+  metric_cc = metric_harness(rgb_cc, gt_rgb, quantize=quant, crop=crop)
   n = rgb.shape[0] * rgb.shape[1]
   flat = lambda x, c=None: x.reshape((n,) if c is None else (n, c)).to(torch.float32).contiguous()
   if config.compute_disp_metrics:                                                    # :148-154
@@ -180,7 +192,8 @@ def evaluate_image(rendering, batch, config, metric_harness=None):
         ops.render_metrics(n, acc=flat(rendering['acc']), alphas=flat(batch.alphas), normals=flat(val, 3),
                            normals_gt=flat(batch.normals, 3), out_normal=out)        # (train_utils' weighted MAE kernel)
         metric[key + '_mae'] = float(out.cpu()[0])
-  images = {'color': rendering['rgb'], 'color_cc': rendering['rgb_cc']}              # :171-188
+  images = {'color': rendering['rgb'], 'color_cc': rendering['rgb_cc']} if postprocess_fn is None else \
+      {'color': rgb, 'color_cc': rgb_cc}                                             # :171-188
   for key in ('distance_mean', 'distance_median', 'normals', 'acc'):
     if rendering.get(key) is not None:
       images[key] = rendering[key]

@@ -1265,6 +1265,127 @@ def vis_matte(x, acc, *, preop=None, origins=None, directions=None, distance=Non
   return out
 
 
+# ----------------------------------------------------------------------------- RawNeRF data path (csrc/raw.hip)
+
+
+def raw_demosaic(mosaic, black=None, white=None, scale=1.0, n_downsample=1, out=None):
+  """raw_utils.load_raw_dataset:354-382 for a stack of RGGB mosaics [N,H,W] (or one [H,W]), uint16 or float32 on the device:
+  (raw - black) / (white - black) * scale in float64 (black, white: per-image float64 device tensors [N], or both None),
+  bilinear_demosaic in float32, area downsample by n_downsample.  Returns [N, H/n, W/n, 3] ([H/n, W/n, 3]) float32."""
+  if mosaic is None or not _on_device(mosaic):
+    raise ValueError('raw_demosaic: mosaic must be a device tensor (the HIP path has no CPU fallback)')
+  if mosaic.dtype not in (torch.uint16, f32):
+    raise ValueError(f'raw_demosaic: mosaic must be uint16 or float32, is {mosaic.dtype}')
+  if not mosaic.is_contiguous():
+    raise ValueError('raw_demosaic: mosaic must be contiguous')
+  single = mosaic.dim() == 2
+  if mosaic.dim() not in (2, 3):
+    raise ValueError(f'raw_demosaic: mosaic must be [H,W] or [N,H,W], is {tuple(mosaic.shape)}')
+  N, H, W = (1,) + tuple(mosaic.shape) if single else tuple(mosaic.shape)
+  n = int(n_downsample)
+  if (black is None) != (white is None):
+    raise ValueError('raw_demosaic: black and white levels go together')
+  for t, nm in ((black, 'black'), (white, 'white')):
+    _chk(t, f64, nm, allow_none=True)
+    if t is not None and t.numel() != N:
+      raise ValueError(f'raw_demosaic: {nm} must hold one level per image ({N}), has {t.numel()}')
+  _chk(out, f32, 'out', allow_none=True)
+  if n < 1 or H % n or W % n:
+    raise ValueError(f'raw_demosaic: n_downsample = {n} must divide the image shape [{H}, {W}]')
+  shape = (N, H // n, W // n, 3)
+  if out is None:
+    out = torch.empty(shape, dtype=f32, device=mosaic.device)
+  elif out.numel() != N * (H // n) * (W // n) * 3:
+    raise ValueError(f'raw_demosaic: out {tuple(out.shape)} must be {shape}')
+  if out.data_ptr() % 8:
+    raise ValueError('raw_demosaic: out must start at a multiple of 8 bytes (the kernel stores pairs of floats)')
+  L.check(lib().mnr_raw_demosaic(N, H, W, L.RAW_DTYPE['float32' if mosaic.dtype == f32 else 'uint16'], _ptr(mosaic), _ptr(black),
+                                 _ptr(white), float(scale), n, _ptr(out), _stream()))
+  return out.reshape(shape[1:] if single else shape)
+
+
+def raw_postprocess(raw, camtorgb, exposure=None, *, linear_only=False, want=('f64',)):
+  """raw_utils.postprocess_raw in float64 on the device: raw [...,3] float32 or float64, camtorgb nine host floats
+  (row-major [3,3]), exposure a host float or a float64 device scalar.  `want`: any of 'f64', 'f32', 'u8'
+  (u8 = utils.save_img_u8's truncation); returns the outputs in that order (one tensor when one is asked for).
+  linear_only: the float64 raw @ camtorgb.T and nothing else."""
+  if raw is None or not _on_device(raw):
+    raise ValueError('raw_postprocess: raw must be a device tensor (the HIP path has no CPU fallback)')
+  if raw.dtype not in (f32, f64):
+    raise ValueError(f'raw_postprocess: raw must be float32 or float64, is {raw.dtype}')
+  if raw.shape[-1] != 3:
+    raise ValueError(f'raw.shape[-1] is {raw.shape[-1]}, expected 3')
+  if not raw.is_contiguous():
+    raise ValueError('raw_postprocess: raw must be contiguous')
+  m = [float(v) for v in camtorgb]
+  if len(m) != 9:
+    raise ValueError(f'raw_postprocess: camtorgb must hold 9 values, has {len(m)}')
+  want = ('f64',) if linear_only else tuple(want)
+  kinds = {'f64': f64, 'f32': f32, 'u8': torch.uint8}
+  if not want or any(w not in kinds for w in want):
+    raise ValueError(f'raw_postprocess: want {want!r} must name some of {sorted(kinds)}')
+  a = L.RawPostArgs()
+  a.P, a.raw, a.raw_f64, a.linear_only = raw.numel() // 3, raw.data_ptr(), int(raw.dtype == f64), int(bool(linear_only))
+  a.camtorgb = (C.c_double * 9)(*m)
+  if isinstance(exposure, torch.Tensor):
+    _chk(exposure, f64, 'exposure')
+    a.exposure_dev = exposure.data_ptr()
+  elif not linear_only:
+    if exposure is None:
+      raise ValueError('raw_postprocess: needs an exposure')
+    a.exposure = float(exposure)
+  outs = {w: torch.empty(raw.shape, dtype=kinds[w], device=raw.device) for w in want}
+  a.out_f64, a.out_f32, a.out_u8 = (None if w not in outs else outs[w].data_ptr() for w in ('f64', 'f32', 'u8'))
+  L.check(lib().mnr_raw_postprocess(C.byref(a), _stream()))
+  res = tuple(outs[w] for w in want)
+  return res[0] if len(res) == 1 else res
+
+
+def quantile_f64(x, p, out=None):
+  """np.percentile(x, p) of a float64 device tensor (flattened; non-finite values ignored) as a float64 device scalar [1]:
+  exact order statistics, numpy's interpolation, no host read."""
+  _chk(x, f64, 'x')
+  _chk(out, f64, 'out', allow_none=True)
+  N = x.numel()
+  nbytes = lib().mnr_quantile_f64_workspace(N)
+  work = torch.empty((max(nbytes, 4) // 4,), dtype=torch.int32, device=x.device)
+  if out is None:
+    out = torch.empty((1,), dtype=f64, device=x.device)
+  L.check(lib().mnr_quantile_f64(N, _ptr(x), float(p), _ptr(work), _ptr(out), _stream()))
+  return out
+
+
+def affine_sums(est, gt, out=None):
+  """The sums behind raw_utils.best_fit_affine(gt, est, axis=(0, 1)): est, gt [...,3] float64 on the device; returns
+  [4,3] float64 on the device: per channel the sums of gt, est, gt * est, gt * gt."""
+  _chk(est, f64, 'est')
+  _chk(gt, f64, 'gt')
+  _chk(out, f64, 'out', allow_none=True)
+  if est.shape != gt.shape or est.shape[-1] != 3:
+    raise ValueError(f'affine_sums: est {tuple(est.shape)} and gt {tuple(gt.shape)} must be two [...,3] images of one shape')
+  P = est.numel() // 3
+  partials = torch.empty((max(lib().mnr_affine_sums_partials(P), 1),), dtype=f64, device=est.device)
+  if out is None:
+    out = torch.empty((4, 3), dtype=f64, device=est.device)
+  L.check(lib().mnr_affine_sums(P, _ptr(est), _ptr(gt), _ptr(partials), _ptr(out), _stream()))
+  return out
+
+
+def affine_apply(est, a, b, out=None):
+  """(est - b) / a per channel: est [...,3] float64 on the device, a and b three host floats each."""
+  _chk(est, f64, 'est')
+  _chk(out, f64, 'out', allow_none=True)
+  if est.shape[-1] != 3 or (out is not None and out.shape != est.shape):
+    raise ValueError(f'affine_apply: est {tuple(est.shape)} (and out) must be [...,3]')
+  a, b = [float(v) for v in a], [float(v) for v in b]
+  if len(a) != 3 or len(b) != 3:
+    raise ValueError('affine_apply: a and b must hold three values each')
+  if out is None:
+    out = torch.empty_like(est)
+  L.check(lib().mnr_affine_apply(est.numel() // 3, _ptr(est), (C.c_double * 3)(*a), (C.c_double * 3)(*b), _ptr(out), _stream()))
+  return out
+
+
 def interlevel_loss(mult, t, w, t_env, w_env, stats, g_w_env, *, B_valid):
   for x, nm in ((t, 't'), (w, 'w'), (t_env, 't_env'), (w_env, 'w_env')):
     _chk(x, f32, nm)

@@ -147,13 +147,12 @@ def main():
   torch.cuda.set_device(dev)
   config = configs.load_preset(args.preset, args.gin_bindings) if args.preset else \
       configs.load_config(args.gin_configs, args.gin_bindings, save_config=False)
-  if config.rawnerf_mode:
-    raise SystemExit('render.py: Config.rawnerf_mode is not supported (no RawNeRF loader, hence no postprocess_fn)')
   cmaps = {}
   if args.colormaps:
     with np.load(args.colormaps) as z:
       cmaps = {k: torch.as_tensor(z[k].astype(np.float32)).to(dev) for k in z.files}
   dataset = datasets.load_dataset('test', config.data_dir, config, device=dev)
+  postprocess_fn = dataset.metadata['postprocess_fn'] if config.rawnerf_mode else None          # render.py:107-110
   model, state, render_eval_pfn, _, _ = train_utils.setup_model(config, 20200823, dataset=dataset, device=dev)
   if not config.checkpoint_dir or checkpoints.latest_checkpoint(config.checkpoint_dir) is None:
     raise SystemExit(f'render.py: no checkpoint in Config.checkpoint_dir = {config.checkpoint_dir!r}')
@@ -211,7 +210,11 @@ def main():
       continue
     print(f'Rendered in {(time.time() - eval_start_time):0.3f}s', flush=True)
 
-    frames = {'color': to_u8(rendering['rgb'])}
+    if postprocess_fn is not None:                                 # render.py:163: raw space -> sRGB, before anything is saved
+      rendering['rgb'], rgb_u8 = postprocess_fn(rendering['rgb'].float(), want=('f32', 'u8'))
+      frames = {'color': rgb_u8.cpu().numpy()}                     # (the kernel's 8-bit output: utils.save_img_u8's truncation)
+    else:
+      frames = {'color': to_u8(rendering['rgb'])}
     save_fn(_save_png, frames['color'], path_fn(f'color_{idx_str}.png'))
     if rendering.get('normals') is not None:
       frames['normals'] = to_u8(rendering['normals'] / 2. + 0.5)

@@ -51,6 +51,7 @@ def main():
   dataset._gen.manual_seed(20200823 + rank)                                              # train.py:99-100
   test_dataset = datasets.load_dataset('test', config.data_dir, config, device=dev)
   cameras = dataset.cameras
+  postprocess_fn = test_dataset.metadata['postprocess_fn'] if config.rawnerf_mode else (lambda z, *a, **k: z)   # train.py:68-72
 
   model, state, render_eval_pfn, train_pstep, lr_fn = train_utils.setup_model(config, 20200823, dataset=dataset, device=dev)
   if rank == 0:
@@ -64,6 +65,11 @@ def main():
   init_step = state.step + 1
   log = open(os.path.join(config.checkpoint_dir, 'train_log.jsonl'), 'a') if (config.checkpoint_dir and rank == 0) else None
 
+  if config.rawnerf_mode and log and init_step == 1:                                     # train.py:101-107 (as text: no TensorBoard)
+    for name, ds in (('train', dataset), ('test', test_dataset)):
+      log.write(json.dumps({'raw_split': name, **{k: np.asarray(ds.metadata[k]).tolist() for k in
+                                                    ('exposure_idx', 'exposure_values', 'unique_shutters')}}) + '\n')
+    log.flush()
   gen = torch.Generator(device=dev).manual_seed(20200823 + rank)
   num_steps = config.early_exit_steps if config.early_exit_steps is not None else config.max_steps
   stats_buffer, train_start, total_time, total_steps = [], time.time(), 0.0, 0
@@ -117,11 +123,11 @@ def main():
       torch.cuda.synchronize()
       if rank == 0:
         h, w = rendering['rgb'].shape[:2]
-        psnr = mse_to_psnr(float(((rendering['rgb'] - test_case.rgb)**2).mean()))
+        pred, true = postprocess_fn(rendering['rgb'].float()), postprocess_fn(test_case.rgb[..., :3].float())   # train.py:246-247
+        psnr = mse_to_psnr(float(((pred - true)**2).mean()))
         extra = {}
         if min(h, w) >= 11:                                  # (an image smaller than the 11 x 11 window has no SSIM)
-          extra['test_ssim'] = float(ops.ssim(rendering['rgb'].float().contiguous(),
-                                              test_case.rgb[..., :3].float().contiguous()).cpu()[0])   # train.py:240
+          extra['test_ssim'] = float(ops.ssim(pred.contiguous(), true.contiguous()).cpu()[0])           # train.py:240
         print(f'Eval {step}: {time.time() - t0:.3f}s, {h * w / (time.time() - t0):.0f} rays/sec, test psnr {psnr:.3f}'
               + ''.join(f', ssim {v:.4f}' for v in extra.values()), flush=True)
         if log:
