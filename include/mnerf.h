@@ -846,6 +846,26 @@ int mnr_affine_sums(int64_t P, const double* est, const double* gt, double* part
 /* raw_utils.match_images_affine's last line: out[i, c] = (est[i, c] - b[c]) / a[c]; a, b: HOST [3]; out may alias est. */
 int mnr_affine_apply(int64_t P, const double* est, const double* a, const double* b, double* out, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Image ingest  (what the dataset loaders do with decoded pixels; csrc/ingest.hip)
+ * ------------------------------------------------------------------------- */
+typedef enum { MNR_IMG_U8 = 0, MNR_IMG_F32 = 1 } mnr_img_dtype;
+typedef enum { MNR_INGEST_PLAIN = 0, MNR_INGEST_WHITE_BG = 1, MNR_INGEST_NORMALS = 2 } mnr_ingest_mode;
+
+/* src: DEVICE [N,H,W,C], 1 <= C <= 4, uint8 or float32 (dtype a mnr_img_dtype).  With n = n_downsample (must divide H and W),
+ * h = H / n, w = W / n, per output pixel and channel the block mean m (image.downsample): uint8: the exact integer sum S
+ * of the n x n block, m = float(S) / float(n n), one float32 division (n <= 256, so that S is exact); float32: the block
+ * added in float64 row by row (dy outer, dx inner), divided by n n in float64 and rounded once.  n = 1: m is the value.
+ * Then, every step rounded to float32 on its own (no fused multiply-add):
+ *   MNR_INGEST_PLAIN     out [N,h,w,C_out] = the first C_out <= C channels of v, v = m / 255.f (uint8) or m (float32);
+ *   MNR_INGEST_WHITE_BG  (C == 4, C_out == 3) out[c] = v[c] * v[3] + (1.f - v[3]); alpha [N,h,w], when not NULL, = v[3];
+ *   MNR_INGEST_NORMALS   (uint8, C >= 3, C_out == 3) out[c] = m[c] * 2.f / 255.f - 1.f.
+ * alpha must be NULL in the other modes.  n * C may not exceed 4096 (only a float32 input can get there).  N == 0 is a
+ * successful no-op.  Invalid arguments return MNR_ERR_INVALID_ARGUMENT before anything is launched.  64-bit offsets; no
+ * atomics: two runs agree bit for bit. */
+int mnr_image_ingest(int N, int H, int W, int C, int dtype, const void* src, int n_downsample, int mode, int C_out,
+                     float* out, float* alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

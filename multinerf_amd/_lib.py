@@ -199,6 +199,10 @@ class RawPostArgs(C.Structure):
               ('exposure_dev', vp), ('linear_only', C.c_int), ('out_f64', vp), ('out_f32', vp), ('out_u8', vp)]
 
 
+IMG_DTYPE = {'uint8': 0, 'float32': 1}         # mnr_img_dtype
+INGEST_MODE = {'plain': 0, 'white_bg': 1, 'normals': 2}      # mnr_ingest_mode
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
@@ -285,6 +289,7 @@ _PROTOS = {
     'mnr_affine_sums_partials': ([i64], i32),
     'mnr_affine_sums': ([i64, vp, vp, vp, vp, vp], i32),
     'mnr_affine_apply': ([i64, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp], i32),
+    'mnr_image_ingest': ([i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

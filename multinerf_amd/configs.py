@@ -332,6 +332,14 @@ NerfMLP.net_width = 128
 """
 
 
+# reference configs/tat.gin: an OVERLAY on a 360 preset ('360+tat') for the Tanks and Temples scenes as processed by NeRF++.
+PRESETS['tat'] = """
+Config.dataset_loader = 'tat_nerfpp'
+Config.near = 0.1
+Config.far = 1e6
+"""
+
+
 def load_preset(name, gin_bindings=None):
   """Clear gin state, bind a named preset or several ('360+debug': left to right, like repeated --gin_configs) and the
   extra bindings, return Config."""

@@ -6,8 +6,16 @@ gather, and rays come from `camera_utils.cast_ray_batch` (csrc/camera.hip) -- ei
 `Config.cast_rays_in_train_step`, inside the train step exactly like the reference's fast path
 (datasets.py:431-433).  Loaders: 'blender' (transforms_*.json + PNG, datasets.py:507-560) and 'procedural'
 (an analytic scene for offline runs; tests/helpers.py uses the same scene) and 'llff' (COLMAP `sparse/0` binaries or
-NGP `transforms.json` poses; forward-facing NDC and 360 scenes, datasets.py:563-712).  DTU / TAT loaders need
-dataset-specific files that cannot be exercised here and are not restated.
+NGP `transforms.json` poses; forward-facing NDC and 360 scenes, datasets.py:563-712), 'tat_nerfpp' (Tanks and Temples as
+processed by NeRF++: `<split>/{pose,intrinsics,rgb}/`, datasets.py:720-765) and 'tat_fvs' (as processed by Free View Synthesis:
+`dense/ibr3d_*/{im_*,Ks.npy,Rs.npy,ts.npy}`, datasets.py:768-830).  'blender' also reads the float TIFF inputs of
+`Config.use_tiffs` (`<file_path>_{R,G,B,A}.tiff`, linear, converted to sRGB) and the `_disp.tiff` disparity maps of
+`Config.compute_disp_metrics`, with Pillow.  The DTU loader needs OpenCV and Config fields the reference does not define,
+and is not restated.
+
+Decoded pixels become device floats in one place, `image.ingest`: on a HIP device the uint8 (or float32) stack is uploaded
+as it is and one kernel (csrc/ingest.hip) downsamples, divides by 255, composites over white or maps normals; with
+device 'cpu' the same float32 expressions run in NumPy.
 
 With `Config.rawnerf_mode` the 'llff' loader reads a raw capture through `raw_utils.load_raw_dataset` (`raw/*.dng` with
 rawpy, or `raw/*.npy` mosaics, plus `raw/*.json` EXIF; the `hdrplus_test/merged` test scenes included): the mosaics are
@@ -179,40 +187,43 @@ class Dataset:
     return self.generate_ray_batch(cam_idx)
 
 
+def _stack_images(paths, channels=None):
+  """The decoded files as one [N,H,W,C] array of their own dtype (uint8, or float32 for mode-F TIFFs); `channels` keeps the
+  first so many."""
+  from PIL import Image
+  imgs = []
+  for p in paths:
+    a = np.asarray(Image.open(p))
+    a = a[..., None] if a.ndim == 2 else a
+    imgs.append(a if channels is None else a[..., :channels])
+  return np.stack(imgs, 0)
+
+
 class Blender(Dataset):
-  """datasets.py:507-560 (PNG path; `use_tiffs` and `_disp.tiff` need a TIFF reader that is not installed)."""
+  """datasets.py:507-560: PNG (or, with Config.use_tiffs, four single-channel float TIFFs per frame) colours, `_normal.png`
+  and `_disp.tiff` maps, all through image.ingest.  A Config.factor that does not divide the image size crops it first."""
 
   def _load_renderings(self, config):
-    from PIL import Image
+    from multinerf_amd import image
     if config.render_path:
       raise ValueError('render_path cannot be used for the blender dataset.')
-    if config.use_tiffs or self._load_disps:
-      raise NotImplementedError('TIFF inputs (use_tiffs / disparity maps) need a TIFF reader')
     with open(os.path.join(self.data_dir, f'transforms_{self.split}.json')) as fp:
       meta = json.load(fp)
-    images, normals, cams = [], [], []
-
-    def get_img(path):
-      im = Image.open(path)
-      if config.factor > 1:                         # image.downsample: area average over factor x factor blocks
-        a = np.asarray(im, dtype=np.float32)
-        h, w = a.shape[0] // config.factor * config.factor, a.shape[1] // config.factor * config.factor
-        a = a[:h, :w].reshape(h // config.factor, config.factor, w // config.factor, config.factor, -1).mean((1, 3))
-        return a
-      return np.asarray(im, dtype=np.float32)
-
-    for frame in meta['frames']:
-      fprefix = os.path.join(self.data_dir, frame['file_path'])
-      images.append(get_img(fprefix + '.png') / 255.)
-      if self._load_normals:
-        normals.append(get_img(fprefix + '_normal.png')[..., :3] * 2. / 255. - 1.)
-      cams.append(np.array(frame['transform_matrix'], dtype=np.float32))
-    images = np.stack(images, 0)
+    prefixes = [os.path.join(self.data_dir, frame['file_path']) for frame in meta['frames']]
+    cams = [np.array(frame['transform_matrix'], dtype=np.float32) for frame in meta['frames']]
+    factor = max(config.factor, 1)
+    if config.use_tiffs:                            # datasets.py:530-533: linear float channels -> sRGB, alpha included
+      tiffs = np.stack([_stack_images([p + f'_{ch}.tiff' for p in prefixes])[..., 0] for ch in 'RGBA'], -1).astype(np.float32)
+      srgba = image.linear_to_srgb(image.ingest(tiffs, factor, 'plain', self.device)).contiguous()
+      self.images, alphas = image.ingest(srgba, 1, 'white_bg', self.device)
+    else:
+      self.images, alphas = image.ingest(_stack_images([p + '.png' for p in prefixes]), factor, 'white_bg', self.device)
+    if self._load_disps:
+      disps = _stack_images([p + '_disp.tiff' for p in prefixes]).astype(np.float32)
+      self.disp_images = image.ingest(disps, factor, 'plain', self.device)[..., 0]
     if self._load_normals:
-      self.normal_images = np.stack(normals, 0)
-      self.alphas = images[..., -1]
-    rgb, alpha = images[..., :3], images[..., -1:]
-    self.images = rgb * alpha + (1. - alpha)        # white background
+      self.normal_images = image.ingest(_stack_images([p + '_normal.png' for p in prefixes]), factor, 'normals', self.device)
+      self.alphas = alphas
     self.height, self.width = self.images.shape[1:3]
     self.camtoworlds = np.stack(cams, 0)
     self.focal = .5 * self.width / np.tan(.5 * float(meta['camera_angle_x']))
@@ -389,7 +400,6 @@ class LLFF(Dataset):
   (raw_utils.load_raw_dataset), the train split at full resolution."""
 
   def _load_renderings(self, config):
-    from PIL import Image
     # the downsampling factor, unless loading the train split of a raw dataset: raw is trained at full resolution because
     # of the Bayer mosaic pattern (datasets.py:570-577)
     use_factor = config.factor > 0 and not (config.rawnerf_mode and self.split == 'train')
@@ -419,8 +429,9 @@ class LLFF(Dataset):
         if not os.path.exists(d):
           raise ValueError(f'Image folder {d} does not exist.')
       colmap_to_image = dict(zip(sorted(os.listdir(colmap_image_dir)), sorted(os.listdir(image_dir))))
-      images = np.stack([np.asarray(Image.open(os.path.join(image_dir, colmap_to_image[f])), dtype=np.float32)[..., :3]
-                         for f in image_names], 0) / 255.
+      from multinerf_amd import image
+      images = image.ingest(_stack_images([os.path.join(image_dir, colmap_to_image[f]) for f in image_names], 3), 1, 'plain',
+                            self.device)
     posefile = os.path.join(self.data_dir, 'poses_bounds.npy')
     bounds = np.load(posefile)[:, -2:] if os.path.exists(posefile) else np.array([0.01, 1.])
     self.colmap_to_world_transform = np.eye(4)
@@ -450,23 +461,82 @@ class LLFF(Dataset):
     all_indices = np.arange(images.shape[0])
     train_indices = all_indices if (config.llff_use_all_images_for_training or raw_testscene) else all_indices % config.llffhold != 0
     indices = {'test': all_indices[all_indices % config.llffhold == 0], 'train': train_indices}[self.split]
-    if config.rawnerf_mode:                             # datasets.py:711-713 (device images: index with a device tensor)
+    if config.rawnerf_mode:                             # datasets.py:711-713
       for key in ('exposure_idx', 'exposure_values'):
         self.metadata[key] = self.metadata[key][indices]
-      indices_t = torch.as_tensor(all_indices[indices]).to(images.device)
-      self.images = images[indices_t]
-    else:
-      self.images = images[indices]
+    self.images = images[torch.as_tensor(all_indices[indices]).to(images.device)]      # (device images: a device index)
     self.camtoworlds = self.render_poses if config.render_path else poses[indices]
     self.height, self.width = self.images.shape[1:3]
 
 
-dataset_dict = {'blender': Blender, 'llff': LLFF, 'procedural': Procedural}
+class TanksAndTemplesNerfPP(Dataset):
+  """datasets.py:720-765: the subset of Tanks and Temples as processed by NeRF++.  `<data_dir>/<split>/{pose,intrinsics,rgb}/`,
+  one 4 x 4 matrix per text file, files paired by sorted order; with Config.render_path the cameras of `camera_path/` at the
+  resolution of the first test image, and no images."""
+
+  def _load_renderings(self, config):
+    from multinerf_amd import image
+    basedir = os.path.join(self.data_dir, 'camera_path' if config.render_path else self.split)
+    files = lambda dirname: [os.path.join(basedir, dirname, f) for f in sorted(os.listdir(os.path.join(basedir, dirname)))]
+    mats = lambda dirname: np.array([np.loadtxt(f) for f in files(dirname)]).reshape(-1, 4, 4)
+    poses = mats('pose') @ np.diag(np.array([1., -1., -1., 1.]))      # flip Y and Z into this code's camera frame
+    intrinsics = mats('intrinsics')                # (all but the first focal length are ignored, as in the reference)
+    if not config.render_path:
+      self.images = image.ingest(_stack_images(files('rgb')), 1, 'plain', self.device)
+      self.height, self.width = self.images.shape[1:3]
+    else:
+      d = os.path.join(self.data_dir, 'test', 'rgb')
+      self.height, self.width = _stack_images([os.path.join(d, sorted(os.listdir(d))[0])]).shape[1:3]
+      self.images = None
+    self.camtoworlds = poses
+    self.focal = intrinsics[0, 0, 0]
+    self.pixtocams = camera_utils.get_pixtocam(self.focal, self.width, self.height).numpy()
+
+
+class TanksAndTemplesFVS(Dataset):
+  """datasets.py:768-830: the subset of Tanks and Temples as processed by Free View Synthesis.  `<data_dir>/dense/ibr3d_*`
+  hold the scene at several sizes; Config.factor indexes them in reversed sorted order.  `Ks.npy`, `Rs.npy`, `ts.npy` are
+  COLMAP world-to-camera; the poses are PCA-aligned, every `llffhold`-th image is held out, and with Config.render_path the
+  test split is an ellipse path (only the first image is read, for its size)."""
+
+  def _load_renderings(self, config):
+    from multinerf_amd import image
+    render_only = config.render_path and self.split == 'test'
+    basedir = os.path.join(self.data_dir, 'dense')
+    sizes = [f for f in sorted(os.listdir(basedir)) if f.startswith('ibr3d')][::-1]
+    if config.factor >= len(sizes):
+      raise ValueError(f'Factor {config.factor} larger than {len(sizes)}')
+    basedir = os.path.join(basedir, sizes[config.factor])
+    files = [f for f in sorted(os.listdir(basedir)) if f.startswith('im_')]
+    if render_only:
+      files = files[:1]
+    pixels = _stack_images([os.path.join(basedir, f) for f in files])
+    intrinsics, rot, trans = (np.load(os.path.join(basedir, f'{n}.npy')) for n in ('Ks', 'Rs', 'ts'))
+    w2c = np.concatenate([rot, trans[..., None]], axis=-1)           # COLMAP world-to-camera -> our camera-to-world
+    c2w = np.linalg.inv(camera_utils.pad_poses(w2c))[:, :3, :4] @ np.diag(np.array([1., -1., -1., 1.]))
+    poses, _ = camera_utils.transform_poses_pca(c2w)                 # z axis up
+    self.poses = poses
+    self.height, self.width = pixels.shape[1:3]
+    self.focal = intrinsics[0, 0, 0]
+    self.pixtocams = camera_utils.get_pixtocam(self.focal, self.width, self.height).numpy()
+    if render_only:
+      self.render_poses = camera_utils.generate_ellipse_path(poses, config.render_path_frames, z_variation=config.z_variation,
+                                                             z_phase=config.z_phase)
+      self.images, self.camtoworlds = None, self.render_poses
+    else:
+      all_indices = np.arange(pixels.shape[0])
+      indices = all_indices[all_indices % config.llffhold == 0] if self.split == 'test' else all_indices[all_indices % config.llffhold != 0]
+      self.images = image.ingest(pixels[indices], 1, 'plain', self.device)         # (only the split's images are uploaded)
+      self.camtoworlds = poses[indices]
+
+
+dataset_dict = {'blender': Blender, 'llff': LLFF, 'procedural': Procedural, 'tat_nerfpp': TanksAndTemplesNerfPP,
+                'tat_fvs': TanksAndTemplesFVS}
 
 
 def load_dataset(split, train_dir, config, device='cuda'):
   """datasets.py:40-52."""
   if config.dataset_loader not in dataset_dict:
     raise NotImplementedError(f'dataset_loader {config.dataset_loader!r}: only {sorted(dataset_dict)} are restated '
-                              '(the others need COLMAP / rawpy data)')
+                              '(the DTU loader needs OpenCV)')
   return dataset_dict[config.dataset_loader](split, train_dir, config, device=device)

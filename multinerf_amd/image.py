@@ -66,6 +66,63 @@ def downsample(img, factor):
   return img.mean((1, 3))
 
 
+def _ingest_host(x, n, mode, c_out):
+  """mnr_image_ingest's arithmetic in NumPy float32 (what the loaders did on the host): (out, alpha or None)."""
+  u8 = x.dtype == np.uint8
+  if n > 1:                                                   # image.downsample: the mean over n x n blocks
+    acc = np.zeros((x.shape[0], x.shape[1] // n, x.shape[2] // n, x.shape[3]), np.uint32 if u8 else np.float64)
+    for dy in range(n):                                       # row by row, the order the kernel adds in
+      for dx in range(n):
+        acc += x[:, dy::n, dx::n]
+    m = acc.astype(np.float32) / np.float32(n * n) if u8 else (acc / np.float64(n * n)).astype(np.float32)
+  else:
+    m = x.astype(np.float32)
+  if mode == 'normals':
+    return m[..., :3] * np.float32(2.) / np.float32(255.) - np.float32(1.), None
+  v = m / np.float32(255.) if u8 else m
+  if mode == 'white_bg':
+    rgb, alpha = v[..., :3], v[..., 3:]
+    return rgb * alpha + (np.float32(1.) - alpha), np.ascontiguousarray(alpha[..., 0])
+  return np.ascontiguousarray(v[..., :c_out]), None
+
+
+def ingest(pixels, factor=1, mode='plain', device='cuda', c_out=None):
+  """The single place where loaders turn decoded pixels into the float32 images a dataset keeps on its device.
+
+  pixels: [N,H,W,C] uint8 or float32, a NumPy array or a tensor.  The area downsample by `factor` (image.downsample), then by
+  `mode`: 'plain' (uint8 `/ 255.`, float32 unchanged; the first `c_out` channels), 'white_bg' (RGBA composited over white,
+  `rgb * alpha + (1. - alpha)`) or 'normals' (uint8 `x * 2. / 255. - 1.`), in the reference's float32 order.  A height or
+  width that `factor` does not divide is cropped at the bottom / right first; the reference's image.downsample raises there.
+
+  On a HIP device the stack is uploaded as it is (bytes stay bytes) and ops.image_ingest does the arithmetic; with
+  device 'cpu' the same expressions are evaluated in NumPy float32 and give the same bits.  Returns the image tensor
+  [N,h,w,c] on `device`, for 'white_bg' the pair (images, alpha [N,h,w])."""
+  device = torch.device(device)
+  n = max(int(factor), 1)
+  x = pixels if isinstance(pixels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pixels))
+  if x.dim() != 4 or x.dtype not in (torch.uint8, torch.float32):
+    raise ValueError(f'ingest: needs [N,H,W,C] uint8 or float32 pixels, got {tuple(x.shape)} {x.dtype}')
+  h, w = x.shape[1] // n * n, x.shape[2] // n * n
+  if h == 0 or w == 0:
+    raise ValueError(f'ingest: factor {n} is larger than the image {tuple(x.shape[1:3])}')
+  x = x[:, :h, :w]
+  if mode not in ('plain', 'white_bg', 'normals'):
+    raise ValueError(f'ingest: unknown mode {mode!r}')
+  if c_out is None:
+    c_out = x.shape[3] if mode == 'plain' else 3
+  if mode == 'white_bg' and x.shape[3] != 4:
+    raise ValueError(f'ingest: mode \'white_bg\' needs RGBA pixels, got {x.shape[3]} channels')
+  if mode == 'normals' and (x.dtype != torch.uint8 or x.shape[3] < 3):
+    raise ValueError('ingest: mode \'normals\' needs uint8 pixels with at least 3 channels')
+  if not 1 <= c_out <= x.shape[3]:
+    raise ValueError(f'ingest: c_out = {c_out} must be between 1 and the {x.shape[3]} channels of the pixels')
+  if device.type == 'cpu':
+    out, alpha = _ingest_host(x.cpu().numpy(), n, mode, c_out)
+    out = torch.from_numpy(np.ascontiguousarray(out))
+    return out if mode != 'white_bg' else (out, torch.from_numpy(alpha))
+  return ops.image_ingest(x.contiguous().to(device), n, mode, c_out, want_alpha=mode == 'white_bg')
+
+
 def solve_warp(gram):
   """The [10,3] warp of one colour-correction iteration from the kernel's [3,65] sums: per channel
   numpy.linalg.lstsq(A^T A, A^T b) in float64.  lstsq and not solve: a grey image makes the system rank deficient, and

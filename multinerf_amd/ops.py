@@ -1446,3 +1446,60 @@ def clip_adam(grad, params, mu, nu, begin, end, sqnorm, *, lr, b1, b2, eps, step
   L.check(lib().mnr_clip_adam(C.byref(cfg), begin, end, _ptr(sqnorm), _ptr(grad), _ptr(params), _ptr(mu),
                               _ptr(nu), _stream()))
   PROFILE.stop(_e, 'clip_adam', 28 * (end - begin))
+
+
+# ----------------------------------------------------------------------------- image ingest (csrc/ingest.hip)
+
+
+def image_ingest(src, n_downsample=1, mode='plain', c_out=None, want_alpha=False, out=None, alpha=None):
+  """Decoded pixels -> the float32 images a dataset keeps: src [N,H,W,C] (or one [H,W,C]), 1 <= C <= 4, uint8 or float32 on
+  the device; the area mean over n_downsample x n_downsample blocks (image.downsample), then by `mode`: 'plain' (`/ 255.` of
+  uint8, float32 as it is; the first c_out channels), 'white_bg' (C = 4: `rgb * alpha + (1. - alpha)`, three channels) or
+  'normals' (uint8: `x * 2. / 255. - 1.` of the first three channels), in the reference's float32 order (mnr_image_ingest).
+  Returns [N,h,w,c_out] float32, and with want_alpha ('white_bg' only) also alpha [N,h,w]."""
+  if src is None or not _on_device(src):
+    raise ValueError('image_ingest: src must be a device tensor (the HIP path has no CPU fallback)')
+  if src.dtype not in (torch.uint8, f32):
+    raise ValueError(f'image_ingest: src must be uint8 or float32, is {src.dtype}')
+  if not src.is_contiguous():
+    raise ValueError('image_ingest: src must be contiguous')
+  if src.dim() not in (3, 4):
+    raise ValueError(f'image_ingest: src must be [H,W,C] or [N,H,W,C], is {tuple(src.shape)}')
+  single = src.dim() == 3
+  N, H, W, Cn = ((1,) if single else ()) + tuple(int(v) for v in src.shape)
+  if mode not in L.INGEST_MODE:
+    raise ValueError(f'image_ingest: mode {mode!r} must be one of {sorted(L.INGEST_MODE)}')
+  if not 1 <= Cn <= 4:
+    raise ValueError(f'image_ingest: src must have 1 to 4 channels, has {Cn}')
+  if c_out is None:
+    c_out = Cn if mode == 'plain' else 3
+  c_out, n = int(c_out), int(n_downsample)
+  if not 1 <= c_out <= Cn:
+    raise ValueError(f'image_ingest: c_out = {c_out} must be between 1 and the {Cn} channels of src')
+  if n < 1 or H % n or W % n:
+    raise ValueError(f'image_ingest: n_downsample = {n} must divide the image shape [{H}, {W}]')
+  if src.dtype == torch.uint8 and n > 256:
+    raise ValueError(f'image_ingest: n_downsample = {n} > 256 is not available for uint8 input')
+  if mode == 'white_bg' and (Cn != 4 or c_out != 3):
+    raise ValueError(f'image_ingest: mode \'white_bg\' needs 4 channels in and 3 out, got {Cn} and {c_out}')
+  if mode == 'normals' and (src.dtype != torch.uint8 or Cn < 3 or c_out != 3):
+    raise ValueError(f'image_ingest: mode \'normals\' needs uint8 input with 3 or 4 channels and c_out = 3')
+  if (want_alpha or alpha is not None) and mode != 'white_bg':
+    raise ValueError('image_ingest: alpha is an output of mode \'white_bg\' only')
+  shape = (N, H // n, W // n, c_out)
+  _chk(out, f32, 'out', allow_none=True)
+  _chk(alpha, f32, 'alpha', allow_none=True)
+  if out is None:
+    out = torch.empty(shape, dtype=f32, device=src.device)
+  elif out.numel() != N * (H // n) * (W // n) * c_out:
+    raise ValueError(f'image_ingest: out {tuple(out.shape)} must be {shape}')
+  if alpha is None and want_alpha:
+    alpha = torch.empty(shape[:3], dtype=f32, device=src.device)
+  elif alpha is not None and alpha.numel() != N * (H // n) * (W // n):
+    raise ValueError(f'image_ingest: alpha {tuple(alpha.shape)} must be {shape[:3]}')
+  L.check(lib().mnr_image_ingest(N, H, W, Cn, L.IMG_DTYPE['float32' if src.dtype == f32 else 'uint8'], _ptr(src), n,
+                                 L.INGEST_MODE[mode], c_out, _ptr(out), _ptr(alpha), _stream()))
+  out = out.reshape(shape[1:] if single else shape)
+  if alpha is None:
+    return out
+  return out, alpha.reshape(shape[1:3] if single else shape[:3])
