@@ -158,6 +158,24 @@ int mnr_cast_rays_ipe_tangent_bwd(const mnr_ipe_cfg* cfg, int64_t B, int n, cons
                                   const float* basis, const uint16_t* g_T_a, const uint16_t* g_T_b, int ld_feat,
                                   float* g_t0, float* g_t1, void* stream);
 
+/* The featurisation of a stand-alone MLP call on CALLER-SUPPLIED Gaussians (replaces MLP.__call__'s own featurisation,
+ * models.py:403-409 with predict_density's :441-449: coord.track_linearize(coord.contract) coord.py:21-60 for a GENERAL
+ * covariance, lift_and_diagonalize :129-133, integrated_pos_enc :102-126 with math.safe_sin math.py:26-38).
+ *  means [M,3], covs [M,9] (row-major 3x3; symmetrised as 0.5 (c_ij + c_ji)): the Gaussians BEFORE warp_fn.
+ *  feat_out: bf16 [M, ld_feat] as mnr_cast_rays_ipe writes it (columns [2KL, ld_feat) zero); feat_f32_out (optional) the same
+ *  features unrounded, fp32 [M, 2KL]; means_out / covs_out (optional, fp32 [M,3] / [M,9]) the POST-warp Gaussians.
+ *  cfg->ray_shape and cfg->disable_integration are not read.  Behind the Gaussian the arithmetic is mnr_cast_rays_ipe's: on
+ *  the Gaussians that call exports without a contraction, the rows are bit-identical. */
+int mnr_ipe_from_gaussians(const mnr_ipe_cfg* cfg, int64_t M, const float* means, const float* covs,
+                           const float* basis, void* feat_out, int ld_feat, float* feat_f32_out,
+                           float* means_out, float* covs_out, void* stream);
+
+/* Tangent rows of the same call (models.py:473-492 via forward mode, as mnr_cast_rays_ipe_tangent): row c*M + s of feat_out
+ * (bf16 [3*M, ld_feat]) = d(IPE features of sample s)/d(mean_c), c = x,y,z, with the covariance an input held fixed; under
+ * cfg->warp_contract the rows carry the contraction's Jacobian and d(J cov J^T)/d(mean_c). */
+int mnr_ipe_from_gaussians_tangent(const mnr_ipe_cfg* cfg, int64_t M, const float* means, const float* covs,
+                                   const float* basis, void* feat_out, int ld_feat, void* stream);
+
 /* coord.pos_enc(viewdirs, 0, deg_view, append_identity=True) per ray, written
  * (bf16) into columns [col0, col0+3+6*deg_view) of every one of the ray's n
  * rows of `dst` [B*n, ld]; columns up to col_end are zero-filled

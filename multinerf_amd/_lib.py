@@ -222,6 +222,8 @@ _PROTOS = {
     'mnr_cast_rays_ipe_tangent': ([C.POINTER(IpeCfg), i64, i32, vp, vp, vp, vp, vp, vp, i32, vp], i32),
     'mnr_cast_rays_ipe_bwd': ([C.POINTER(IpeCfg), i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp], i32),
     'mnr_cast_rays_ipe_tangent_bwd': ([C.POINTER(IpeCfg), i64, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp], i32),
+    'mnr_ipe_from_gaussians': ([C.POINTER(IpeCfg), i64, vp, vp, vp, vp, i32, vp, vp, vp, vp], i32),
+    'mnr_ipe_from_gaussians_tangent': ([C.POINTER(IpeCfg), i64, vp, vp, vp, vp, i32, vp], i32),
     'mnr_sdist_bwd': ([C.POINTER(SdistBwdArgs), vp], i32),
     'mnr_viewdir_enc_fill': ([i64, i32, vp, i32, vp, i32, i32, i32, vp], i32),
     'mnr_pixels_to_rays': ([i64, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp], i32),

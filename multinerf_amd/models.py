@@ -185,6 +185,21 @@ class MLP:
       bad.append('num_rgb_channels != 3')
     return bad
 
+  # `Model.build` attaches the model and this MLP's plan (not dataclass fields: hyper-parameters stay the gin surface)
+  _model = None
+  _plan = None
+
+  def __call__(self, rng, gaussians, viewdirs=None, imageplane=None, glo_vec=None, exposure=None, noise=None):
+    """models.py:403-409,604-612: evaluate this MLP on caller-supplied Gaussians (means [..., n, 3], covs [..., n, 3, 3], BEFORE
+    warp_fn) with the parameters bound to its model -> dict(density, rgb, raw_grad_density, grad_pred, normals, normals_pred,
+    roughness) in the caller's leading shape.  Inference only (`Model.mlp_call`)."""
+    m = self._model
+    if m is None or not m._built or getattr(m, '_bound_flat', None) is None:
+      raise RuntimeError('this MLP is not attached to a built model with bound parameters: Model.build() and Model.bind() '
+                         '(or construct_model) come first')
+    return m.mlp_call(self._plan, rng, gaussians, viewdirs=viewdirs, imageplane=imageplane, glo_vec=glo_vec, exposure=exposure,
+                      noise=noise)
+
 
 @gin.configurable
 @dataclasses.dataclass
@@ -491,6 +506,10 @@ class Model:
       p.basis_dev = torch.as_tensor(p.basis, dtype=f32, device=self.device).contiguous()
       self._layout_packed(p)
     self._ws: Dict[Any, torch.Tensor] = {}
+    # MLP.__call__ (models.py:403-409): the hyper-parameter objects the callers hold evaluate their MLP through this model
+    self.nerf_hp._model, self.nerf_hp._plan = self, self.nerf_plan
+    if self.prop_hp is not self.nerf_hp:
+      self.prop_hp._model, self.prop_hp._plan = self, self.prop_plan
     self._built = True
     return self
 
@@ -1096,16 +1115,17 @@ class Model:
                           head_out=raw_density)
     return dict(acts=[], bits=[], raw_density=raw_density, chain=True)
 
-  def _tangent_forward(self, plan: MLPPlan, tdist, R, M, bits, keep, tag, zs=None):
+  def _tangent_forward(self, plan: MLPPlan, tdist, R, M, bits, keep, tag, zs=None, T_feat=None):
     """Density-gradient normals by forward mode (models.py:473-492 without a second autodiff pass): the three
     tangent feature rows d features / d mean_c of every sample run through the trunk as 3 * M extra GEMM rows whose ReLU is the
     primal layer's 1-bit mask; the density column of the last layer gives raw_grad [3, M]."""
     hp = plan.hp
-    T_feat = self._buf((tag, 'T_feat'), (3 * M, plan.ldF), bf16)
-    ops.cast_rays_ipe_tangent(tdist, R.origins, R.directions, R.radii.reshape(-1).contiguous(), plan.basis_dev,
-                              ray_shape=self.ray_shape, min_deg=hp.min_deg_point, max_deg=hp.max_deg_point,
-                              ld_feat=plan.ldF, out=T_feat, warp_contract=(hp.warp_fn == 'contract'),
-                              disable_integration=self.disable_integration)
+    if T_feat is None:                                    # (given: pre-built tangent rows [3 M, ldF], `mlp_call`)
+      T_feat = self._buf((tag, 'T_feat'), (3 * M, plan.ldF), bf16)
+      ops.cast_rays_ipe_tangent(tdist, R.origins, R.directions, R.radii.reshape(-1).contiguous(), plan.basis_dev,
+                                ray_shape=self.ray_shape, min_deg=hp.min_deg_point, max_deg=hp.max_deg_point,
+                                ld_feat=plan.ldF, out=T_feat, warp_contract=(hp.warp_fn == 'contract'),
+                                disable_integration=self.disable_integration)
     T_acts, T_pre = [], []
     t = None
     relu = hp.net_activation == 'relu'
@@ -1165,8 +1185,9 @@ class Model:
     self._T_pre = T_pre                                   # (non-ReLU activations: the tangent pre-activations, for _tangent_backward)
     return T_feat, T_acts, raw_grad
 
-  def _mlp_forward(self, plan: MLPPlan, flat, feat, M, n, R, tag, keep, tdist=None, bnoise=None, group=None):
-    """MLP.__call__ (models.py:402-612) for the M = B*n samples of one level."""
+  def _mlp_forward(self, plan: MLPPlan, flat, feat, M, n, R, tag, keep, tdist=None, bnoise=None, group=None, T_feat=None):
+    """MLP.__call__ (models.py:402-612) for the M = B*n samples of one level.  `T_feat`: pre-built tangent rows for the
+    density-gradient normals (`mlp_call`: the caller's Gaussians have no ray to cast); None = cast them from the rays."""
     hp = plan.hp
     chain = self._chain_ok(plan)
     if chain and not plan.has_rgb:
@@ -1240,7 +1261,7 @@ class Model:
         raw_density.copy_(small[:, 0])
         raw_grad = None
         if plan.tangent:
-          T_feat, T_acts, raw_grad = self._tangent_forward(plan, tdist, R, M, bits, keep, tag, zs=zs)
+          T_feat, T_acts, raw_grad = self._tangent_forward(plan, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
           res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, T_pre=self._T_pre)
         normals, npred, rough = ops.ref_head_fwd(small, raw_grad, R.viewdirs, n, plan.ide, hp.roughness_bias, VI,
                                                  bw, plan.ldVI, features=plan.features, deg_view=hp.deg_view)
@@ -1267,10 +1288,12 @@ class Model:
       if plan.dn:
         # density-gradient normals without the rest of the Ref-NeRF head (models.py:478-492): for the renderings and the
         # orientation loss; they do not enter the colour
-        T_feat, T_acts, raw_grad = self._tangent_forward(plan, tdist, R, M, bits, keep, tag, zs=zs)
+        T_feat, T_acts, raw_grad = self._tangent_forward(plan, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
         res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, normals=ops.density_normals_fwd(raw_grad), T_pre=self._T_pre)
       if plan.glo > 0:
-        ops.glo_fill(self._glo_table(flat), self._glo_cam, M // n, n, VI, plan.glo_col)
+        # (`mlp_call` feeds the caller's glo_vec as a table of its own, one row per ray)
+        glo_table = getattr(R, 'glo_table', None)
+        ops.glo_fill(self._glo_table(flat) if glo_table is None else glo_table, self._glo_cam, M // n, n, VI, plan.glo_col)
       if bnoise is not None:
         # bottleneck += bottleneck_noise * N(0, 1) (models.py:530-533): additive, so the backward pass is unchanged
         ops.add_noise_bf16(VI, bw, bnoise, hp.bottleneck_noise)
@@ -1340,6 +1363,216 @@ class Model:
   def _glo_table(self, flat):
     G = self.num_glo_features
     return flat[self.glo_off:self.glo_off + self.num_glo_embeddings * G].view(self.num_glo_embeddings, G)
+
+  # ------------------------------------------------------------------ MLP.__call__ on caller-supplied Gaussians
+
+  @_in_library
+  def mlp_call(self, plan: MLPPlan, rng, gaussians, viewdirs=None, imageplane=None, glo_vec=None, exposure=None, noise=None):
+    """MLP.__call__ (models.py:403-409,604-612) of the MLP `plan` on the bound parameters: what `model.nerf_hp(...)` /
+    `model.prop_hp(...)` run.  gaussians = (means [..., n, 3], covs [..., n, 3, 3]): fp32 device tensors, the Gaussians BEFORE
+    warp_fn; viewdirs [..., 3] / glo_vec [..., G] per ray where the MLP reads them; imageplane / exposure are accepted and
+    unused, as in the reference.  rng None: deterministic; a torch.Generator or a seed draws density_noise / bottleneck_noise
+    as `_forward` does; noise = {'density_noise': [..., n] (or one value), 'bottleneck_noise': [..., n, bottleneck]} overrides
+    the draw.  Inference only: nothing is kept for a backward pass, and the activation buffers are the call's own
+    (('mlpcall', module)), so a call between a training forward pass and its backward pass touches no ('lvl', ...) buffer,
+    `_saved` or `_T_pre`.  PRECONDITION for such a call: the bound parameters are the tensor that forward pass ran on (what
+    construct_model + train_utils give: the parameters are updated in place).  The call re-packs the bound parameters into
+    the shared operand images (`pack_weights`: every plan's wbf / head_bias) and, for padded trunk widths, into the shared
+    execution-layout vector (`_to_exec`), both of which a pending backward pass reads; after
+    `model.apply(other_flat, ..., keep_for_backward=True)` an MLP call on differently bound parameters would hand that backward
+    pass the wrong weights.
+
+    All rows are evaluated at once (features, three tangent rows per sample with density-gradient normals, every layer's
+    activations: a few KiB per sample); a caller with many samples, e.g. the grid of a mesh extraction, passes them in chunks.
+
+    The featurisation is mnr_ipe_from_gaussians (csrc/gaussians.hip); behind it the Dense layers, heads and the density /
+    colour activations are the level loop's own kernels (`_mlp_forward`, mnr_composite_fwd on a dummy step function), every
+    sample a ray of its own, the rows padded to the GEMM tile by repeating the last sample."""
+    import types
+    if not self._built or getattr(self, '_bound_flat', None) is None:
+      raise RuntimeError('Model.mlp_call needs a built model with bound parameters (Model.build, Model.bind)')
+    hp, dev = plan.hp, self.device
+    try:
+      means, covs = gaussians
+    except (TypeError, ValueError):
+      raise ValueError('gaussians must be a pair (means [..., n, 3], covs [..., n, 3, 3])') from None
+
+    def want(t, name, shape=None, last=None):
+      if not torch.is_tensor(t) or not ops._on_device(t) or t.dtype != f32:
+        raise ValueError(f'{name} must be a float32 device tensor (the HIP path has no CPU fallback)')
+      if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name} must have shape {tuple(shape)}, has {tuple(t.shape)}')
+
+    want(means, 'means')
+    if means.dim() < 2 or means.shape[-1] != 3 or means.numel() == 0:
+      raise ValueError(f'means must be [..., n, 3], is {tuple(means.shape)}')
+    # (the full matrix: coord.lift_and_diagonalize takes no diagonal covariance, coord.py:129-133)
+    want(covs, 'covs', tuple(means.shape) + (3,))
+    lead = tuple(means.shape[:-1])
+    ray_lead, n = lead[:-1], lead[-1]
+    M0 = int(np.prod(lead))
+    rays = M0 // n
+    Mp = _rup(M0, 256)
+
+    def rows(t, cols):
+      """[M0, cols] -> [Mp, cols], the last sample repeated."""
+      t = t.reshape(M0, cols)
+      if Mp != M0:
+        t = torch.cat([t, t[-1:].expand(Mp - M0, cols)], 0)
+      return t.contiguous()
+
+    def per_sample(t, cols):
+      """A per-ray [..., cols] input as one row per (padded) sample."""
+      return rows(t.reshape(rays, 1, cols).expand(rays, n, cols), cols)
+
+    vd = glo_tab = None
+    if plan.use_viewdirs:
+      if viewdirs is None:
+        raise ValueError(f'{plan.module_name} was built with view directions: viewdirs [..., 3] is required')
+      want(viewdirs, 'viewdirs', ray_lead + (3,))
+      vd = per_sample(viewdirs, 3)
+    if plan.glo > 0:
+      if glo_vec is None:
+        raise ValueError(f'{plan.module_name} reads {plan.glo} GLO features: glo_vec [..., {plan.glo}] is required')
+      want(glo_vec, 'glo_vec', ray_lead + (plan.glo,))
+      glo_tab = per_sample(glo_vec, plan.glo)
+    # (a glo_vec / viewdirs given to an MLP that reads none is ignored, as the reference ignores it)
+
+    flat = self._to_exec(self._bound_flat)
+    # A density-only MLP on the fused chain is evaluated by Model.__call__ without a backward pass (render / eval) with layer
+    # 0's K walked group-major (mnr_mlp_chain_fwd_ipe, `_chain_forward_ipe`); the call takes the same form, so that it returns
+    # what such a pass returns, bit for bit (`_chain_forward_grouped`)
+    grouped = bool(_FUSED_IPE and self._ipe_chain_ok(plan))
+    self.pack_weights(flat, ipe=grouped)
+
+    nz = noise or {}
+    randomized = (rng is not None) or (noise is not None)
+    gen = None
+    if rng is not None:
+      gen = rng if isinstance(rng, torch.Generator) else torch.Generator(device=dev).manual_seed(int(rng))
+    bnoise = None
+    if randomized and plan.has_rgb and plan.use_viewdirs and hp.bottleneck_noise > 0:      # models.py:530-533, as `_forward`
+      bw_ = hp.bottleneck_width
+      bw_t = self._tplans[self._plans.index(plan)].hp.bottleneck_width
+      if 'bottleneck_noise' in nz:
+        bnoise = nz['bottleneck_noise'].to(dev).float().reshape(M0, bw_t)
+      elif gen is not None:
+        bnoise = torch.randn((M0, bw_t), generator=gen, device=dev, dtype=f32)
+      if bnoise is not None:
+        if bw_ != bw_t:
+          bnoise = torch.cat([bnoise, bnoise.new_zeros((M0, bw_ - bw_t))], 1)
+        bnoise = rows(bnoise, bw_)
+    dnoise = None
+    if randomized and hp.density_noise > 0:                                                  # models.py:462-464, as `_forward`
+      if 'density_noise' in nz:
+        dnoise = nz['density_noise'].to(dev).float()
+        dnoise = dnoise.reshape(1, 1).expand(M0, 1) if dnoise.numel() == 1 else dnoise.reshape(M0, 1)
+      elif gen is not None:
+        dnoise = (torch.randn((1, 1), generator=gen, device=dev, dtype=f32).expand(M0, 1) if plan.tangent
+                  else torch.randn((M0, 1), generator=gen, device=dev, dtype=f32))
+      if dnoise is not None:
+        dnoise = rows(dnoise, 1)
+
+    tag = ('mlpcall', plan.module_name)
+    g_means, g_covs = rows(means, 3), rows(covs, 9)
+    ipe_kw = dict(warp_contract=(hp.warp_fn == 'contract'), min_deg=hp.min_deg_point, max_deg=hp.max_deg_point, ld_feat=plan.ldF)
+    feat = self._buf((tag, 'feat'), (Mp, plan.ldF), bf16)
+    ops.ipe_from_gaussians(g_means, g_covs, plan.basis_dev, out=feat, **ipe_kw)
+    T_feat = None
+    if plan.tangent:
+      T_feat = self._buf((tag, 'T_feat'), (3 * Mp, plan.ldF), bf16)
+      ops.ipe_from_gaussians_tangent(g_means, g_covs, plan.basis_dev, out=T_feat, **ipe_kw)
+
+    R = types.SimpleNamespace(viewdirs=vd, radii=None, origins=None, directions=None, glo_table=glo_tab)
+    missing = object()
+    keep_cam, keep_tpre = getattr(self, '_glo_cam', missing), getattr(self, '_T_pre', missing)
+    try:
+      if glo_tab is not None:
+        self._glo_cam = self._const(('mlpcall', 'glo_idx'), (Mp,), lambda: torch.arange(Mp, dtype=torch.int32, device=dev))
+      if grouped:
+        out = self._chain_forward_grouped(plan, flat, feat, Mp, tag)
+      else:
+        out = self._mlp_forward(plan, flat, feat, Mp, 1, R, tag, False, bnoise=bnoise, T_feat=T_feat)
+    finally:
+      for name, val in (('_glo_cam', keep_cam), ('_T_pre', keep_tpre)):
+        if val is missing:
+          self.__dict__.pop(name, None)
+        else:
+          setattr(self, name, val)
+
+    # density = act(raw + noise + bias), colour = act(premultiplier * raw + bias) padded (models.py:506,584-602): per sample
+    # inside mnr_composite_fwd, the kernel the level loop takes both from; its step function here is a dummy (32 samples per row
+    # of [0, 1]; weights and the composited colour are not used).
+    nc = 32
+    ccfg = ops.composite_cfg(nc, opaque_background=False, density_act=hp.density_activation, density_bias=hp.density_bias,
+                             density_noise_std=hp.density_noise if dnoise is not None else 0.0, has_rgb=plan.has_rgb,
+                             rgb_act='identity' if plan.diffuse_on else hp.rgb_activation,
+                             rgb_premultiplier=1.0 if plan.diffuse_on else hp.rgb_premultiplier,
+                             rgb_bias=0.0 if plan.diffuse_on else hp.rgb_bias,
+                             rgb_padding=0.0 if plan.diffuse_on else hp.rgb_padding, bg_mode=0, bg_value=0.0)
+    t_dummy = self._const(('mlpcall', 'tdist'), (Mp, nc),
+                          lambda: torch.linspace(0., 1., nc + 1, dtype=f32).to(dev).repeat(Mp // nc, 1).contiguous())
+    d_dummy = self._const(('mlpcall', 'dirs'), (Mp, nc), lambda: torch.ones((Mp // nc, 3), dtype=f32, device=dev))
+    density, rgb, _, _, _ = ops.composite_fwd(
+        ccfg, out['raw_density'].view(Mp // nc, nc), t_dummy, d_dummy,
+        raw_rgb=out['raw_rgb'].view(Mp // nc, nc, 3) if plan.has_rgb else None,
+        density_noise=dnoise.view(Mp // nc, nc) if dnoise is not None else None, want_acc=False)
+
+    def shaped(t, cols=None):
+      """The first M0 rows of a per-sample result, in the caller's leading shape, as a tensor of its own."""
+      if t is None:
+        return None
+      t = t.reshape(Mp, -1)[:M0]
+      return t.reshape(lead + ((cols,) if cols else ())).clone()
+
+    return dict(
+        density=shaped(density),
+        rgb=shaped(rgb, 3) if rgb is not None else torch.zeros(lead + (3,), dtype=f32, device=dev),
+        raw_grad_density=shaped(out['raw_grad'].t(), 3) if plan.tangent else None,
+        grad_pred=shaped(out['small'][:, 1:4], 3) if hp.enable_pred_normals else None,
+        normals=shaped(out['normals'], 3) if plan.tangent else None,
+        normals_pred=shaped(out['npred'], 3) if hp.enable_pred_normals else None,
+        roughness=shaped(out['rough'], 1) if out.get('rough') is not None else None)
+
+  def _chain_forward_grouped(self, plan: MLPPlan, flat, feat, M, tag):
+    """`_chain_forward_ipe` for a feature matrix that already exists (`mlp_call`): the rows' columns are moved into the
+    group-major order of the in-kernel producer (four degrees per group of MNR_CHAIN_IPE_GROUP_COLS columns, the rest zero;
+    a copy, no arithmetic) and mnr_mlp_chain_fwd runs on layer 0's group-major image 'trunk0_ipe'.  Same bf16 features, same
+    operand, same order of the MFMA accumulation over K: the head output is mnr_mlp_chain_fwd_ipe's, bit for bit
+    (tests/test_gpu_mlp_call.py, blender_256's proposal level)."""
+    G, K, Ld, W = L.CHAIN_IPE_GROUP_COLS, plan.K, plan.L, plan.W
+    ld_g = (Ld // 4) * G
+
+    def perm():
+      src = [sc * K * Ld + l * K + k for l in range(Ld) for sc in range(2) for k in range(K)]
+      dst = [(l // 4) * G + (l % 4) * 2 * K + sc * K + k for l in range(Ld) for sc in range(2) for k in range(K)]
+      return (torch.tensor(src, dtype=torch.int64, device=self.device), torch.tensor(dst, dtype=torch.int64, device=self.device))
+
+    src, dst = self._const(('mlpcall', 'group_perm', plan.module_name), (K, Ld, G), perm)
+    feat_g = self._buf((tag, 'feat_g'), (M, ld_g), bf16, zero=True)          # (the columns outside `dst` stay zero)
+    feat_g.index_copy_(1, dst, feat.index_select(1, src))
+    layers = []
+    for i, (d, _) in enumerate(plan.trunk):
+      e = plan.packed['trunk0_ipe' if i == 0 else ('trunk', i)]
+      layers.append((self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), flat[d.bias_off:d.bias_off + d.fan_out]))
+    e = plan.packed['density']
+    d = plan.density
+    raw_density = self._buf((tag, 'raw_density'), (M,), f32)
+    ops.mlp_chain_fwd(feat_g, ld_g, layers, M=M, W=W, w_head=self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])[0],
+                      b_head=flat[d.bias_off:d.bias_off + 1], head_out=raw_density)
+    return dict(acts=[], bits=[], raw_density=raw_density, chain=True)
+
+  def query_density(self, xyz, std=0.0):
+    """The NeRF level's density at the points xyz [..., 3] (isotropic Gaussians of standard deviation `std`): the query a
+    mesh extraction makes.  Density does not depend on the view direction or the GLO vector; where the MLP reads them they
+    are fed a constant.  One `mlp_call` over all points (its precondition and its memory use apply): a large grid is passed
+    in chunks by the caller."""
+    plan, dev = self.nerf_plan, self.device
+    gaussians = points_to_gaussians(xyz, std)
+    lead = tuple(gaussians[0].shape[:-2])
+    vd = torch.tensor([0., 0., 1.], dtype=f32, device=dev).expand(lead + (3,)).contiguous() if plan.use_viewdirs else None
+    glo = torch.zeros(lead + (plan.glo,), dtype=f32, device=dev) if plan.glo > 0 else None
+    return self.mlp_call(plan, None, gaussians, viewdirs=vd, glo_vec=glo)['density']
 
   @_in_library
   def backward_level(self, lv, flat, grads, g_rgb_out, g_weights, g_expo=None, g_normals=None, g_npred=None, losses=None,
@@ -1803,6 +2036,13 @@ class Model:
 
 
 # =============================================================================
+
+
+def points_to_gaussians(xyz, std=0.0):
+  """Points xyz [..., n, 3] as the isotropic Gaussians (means, covs [..., n, 3, 3] = std^2 I) an MLP call takes
+  (`MLP.__call__`, `Model.query_density`); std = 0 is a point query."""
+  eye = torch.eye(3, dtype=xyz.dtype, device=xyz.device) * (float(std) ** 2)
+  return xyz.contiguous(), eye.expand(tuple(xyz.shape[:-1]) + (3, 3)).contiguous()
 
 
 def construct_model(rng, rays, config, device='cuda'):

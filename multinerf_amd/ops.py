@@ -267,6 +267,57 @@ def cast_rays_ipe_tangent(tdist, origins, directions, radii, basis, *, ray_shape
   return out
 
 
+def _chk_gaussians(means, covs, basis):
+  for x, nm in ((means, 'means'), (covs, 'covs'), (basis, 'basis')):
+    _chk(x, f32, nm)
+  if means.dim() != 2 or means.shape[1] != 3 or means.shape[0] == 0:
+    raise ValueError(f'means must be [M, 3], is {tuple(means.shape)}')
+  M = means.shape[0]
+  if covs.numel() != M * 9 or covs.shape[0] != M:
+    raise ValueError(f'covs must be [M, 9] or [M, 3, 3] (full covariances), is {tuple(covs.shape)}')
+  return M
+
+
+def ipe_from_gaussians(means, covs, basis, *, warp_contract, min_deg, max_deg, ld_feat, out=None, want_f32=False,
+                       want_gaussians=False):
+  """Caller-supplied Gaussians (means [M,3], covs [M,9] / [M,3,3], BEFORE the warp) -> bf16 features [M, ld_feat] as
+  `cast_rays_ipe` writes them (+ optional fp32 features [M, 2KL], + optional post-warp means [M,3], covs [M,9])."""
+  M = _chk_gaussians(means, covs, basis)
+  cfg = _ipe_cfg('cone', warp_contract, False, basis, min_deg, max_deg)         # (ray_shape / disable_integration: not read)
+  dev = means.device
+  if out is None:
+    out = torch.empty((M, ld_feat), dtype=act_dtype(), device=dev)
+  _chk(out, bf16, 'out')
+  assert out.shape == (M, ld_feat)
+  feat32 = gm = gc = None
+  if want_f32:
+    feat32 = torch.empty((M, 2 * basis.shape[0] * (max_deg - min_deg)), dtype=f32, device=dev)
+  if want_gaussians:
+    gm = torch.empty((M, 3), dtype=f32, device=dev)
+    gc = torch.empty((M, 9), dtype=f32, device=dev)
+  _e = PROFILE.start()
+  L.check(lib().mnr_ipe_from_gaussians(C.byref(cfg), M, _ptr(means), _ptr(covs), _ptr(basis), _ptr(out), ld_feat, _ptr(feat32),
+                                       _ptr(gm), _ptr(gc), _stream()))
+  PROFILE.stop(_e, 'ipe', 48 * M + 2 * out.numel())
+  if not (want_f32 or want_gaussians):
+    return out
+  return (out,) + ((feat32,) if want_f32 else ()) + ((gm, gc) if want_gaussians else ())
+
+
+def ipe_from_gaussians_tangent(means, covs, basis, *, warp_contract, min_deg, max_deg, ld_feat, out=None):
+  """-> bf16 [3*M, ld_feat]: rows c*M + s = d(features of sample s)/d(mean_c), the covariance held fixed (as
+  `cast_rays_ipe_tangent`, for caller-supplied Gaussians)."""
+  M = _chk_gaussians(means, covs, basis)
+  cfg = _ipe_cfg('cone', warp_contract, False, basis, min_deg, max_deg)
+  if out is None:
+    out = torch.empty((3 * M, ld_feat), dtype=act_dtype(), device=means.device)
+  _chk(out, bf16, 'out')
+  assert out.shape == (3 * M, ld_feat)
+  L.check(lib().mnr_ipe_from_gaussians_tangent(C.byref(cfg), M, _ptr(means), _ptr(covs), _ptr(basis), _ptr(out), ld_feat,
+                                               _stream()))
+  return out
+
+
 def cast_rays_ipe_bwd(tdist, origins, directions, radii, basis, g_feat_a, g_feat_b=None, *, ray_shape, warp_contract, min_deg,
                       max_deg, disable_integration=False, g_t0=None, g_t1=None):
   """VJP of `cast_rays_ipe` w.r.t. the interval ends: g_feat_a (+ g_feat_b) bf16 [B*n, ld] -> (g_t0, g_t1) fp32 [B*n]."""

@@ -1,0 +1,57 @@
+"""MLP.__call__ on caller-supplied Gaussians, without a GPU: the two C entries are declared and bound, the source file is on
+every build list, an MLP that belongs to no built model refuses the call, and the documents describe the callable."""
+
+import os
+
+import pytest
+import torch
+
+from multinerf_amd import _lib, build, models
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ('mnr_ipe_from_gaussians', 'mnr_ipe_from_gaussians_tangent')
+
+
+def test_header_declares_and_protos_bind_both_entries():
+  names = _lib.header_symbols()
+  for e in ENTRIES:
+    assert e in names and e in _lib._PROTOS and e not in _lib.F32_ABSENT
+  # (cfg, M, means, covs, basis, feat_out, ld_feat, feat_f32_out, means_out, covs_out, stream) / (..., feat_out, ld_feat, stream)
+  assert len(_lib._PROTOS[ENTRIES[0]][0]) == 11 and len(_lib._PROTOS[ENTRIES[1]][0]) == 8
+  with open(_lib.HEADER_PATH) as f:
+    text = f.read()
+  assert 'models.py:403-409' in text                      # the reference lines the entries replace
+
+
+def test_source_file_is_on_every_build_list():
+  assert 'gaussians.hip' in build.SOURCES and 'gaussians.hip' in build.SOURCES_F32
+  for rel in ('tools/hipsim/build.py', 'tools/isa_report.py'):
+    with open(os.path.join(ROOT, rel)) as f:
+      assert "'gaussians.hip'" in f.read(), rel
+  with open(os.path.join(build.CSRC, 'gaussians.hip')) as f:
+    src = f.read()
+  assert '#pragma clang fp contract(off)' in src and '#include "ipe_math.h"' in src
+
+
+def test_mlp_of_an_unbuilt_model_raises():
+  model = models.Model()
+  g = (torch.zeros((1, 4, 3)), torch.zeros((1, 4, 3, 3)))
+  for mlp in (model.nerf_hp, model.prop_hp, models.NerfMLP()):
+    with pytest.raises(RuntimeError, match='not attached'):
+      mlp(None, g, viewdirs=torch.zeros((1, 3)))
+
+
+def test_points_to_gaussians():
+  xyz = torch.arange(12, dtype=torch.float32).reshape(2, 2, 3)
+  means, covs = models.points_to_gaussians(xyz, 0.5)
+  assert torch.equal(means, xyz) and covs.shape == (2, 2, 3, 3)
+  assert torch.equal(covs, (0.25 * torch.eye(3)).expand(2, 2, 3, 3))
+  assert (models.points_to_gaussians(xyz)[1] == 0).all()
+
+
+def test_documents_describe_the_callable():
+  with open(os.path.join(ROOT, 'README.md')) as f:
+    readme = f.read()
+  assert 'not callable' not in readme and 'model.nerf_hp(' in readme and 'query_density' in readme
+  with open(os.path.join(ROOT, 'INTEGRATION.md')) as f:
+    assert 'mnr_ipe_from_gaussians' in f.read()
