@@ -46,13 +46,22 @@ def _in_library(fn):
   return wrapped
 
 
-def _rank1_last(plan, D, W, feature_gradient):
-  """Whether the last hidden layer's dY = relu'(z) * (g (x) w_density) of a Dense(1)-headed chain (the proposal MLP, reference
-  models.py:457-460) can stay unstored: its weight-gradient GEMM then builds it from the factors (`mnr_gemm_tn_args.rank1_*`).  Not
-  when another reader needs the matrix (a skip concat's second GEMM, the feature gradient of a one-layer trunk)."""
-  concat_last = bool(plan.trunk[D - 1][1])
-  k_in = plan.ldF if D == 1 else W
-  return bool(_RANK1_LAST and W % 256 == 0 and k_in % 256 == 0 and not concat_last and not (feature_gradient and D == 1))
+@dataclasses.dataclass(frozen=True)
+class Route:
+  """How one MLP runs for one level of one call (`Model._route`): decided once, before the level's first launch, from the module
+  switches as they stand then; the forward pass acts on it and hands it to the backward pass in its result (`mlp['route']`)."""
+  chain: bool         # the whole density-only MLP as the fused chain, its Dense(1) head inside the kernel (`_chain_forward`)
+  chain_trunk: bool   # the trunk as the fused chain, the heads per-layer GEMMs on its output (`_chain_trunk`)
+  ipe: bool           # the fused chain builds its own IPE features (`_chain_forward_ipe`; `mlp_call`: `_chain_forward_grouped`)
+  panel: bool         # the per-layer trunk's activations / masks / gradients in panel storage (`_panel_ok`)
+  vcol: bool          # the density head's forward column as a vector next to the bottleneck GEMM (`_HEAD_VCOL`)
+  gcol: bool          # the density head's weight gradient as a vector column of the bottleneck's dW GEMM (`_head_gcol`)
+  need_bits: bool     # the per-layer / chain trunk writes 1-bit ReLU masks (backward pass, tangent network)
+
+  @property
+  def fused(self):
+    """The trunk runs on the fused chain kernels, with or without its head (`Model._chain_ok`)."""
+    return self.chain or self.chain_trunk
 
 
 # Module-level switches of the host orchestration.  Every one of them was a same-box A/B in rounds 2-4 (profiles/HISTORY.md,
@@ -226,6 +235,10 @@ class DenseSpec:
   bias_off: int = 0
   in_segs: Tuple[int, ...] = ()   # widths of the concatenated blocks its input rows are made of (trunk | features | ...): what
                                   # Model.build maps between the callers' layout and a zero-padded execution layout
+
+  def bias(self, flat):
+    """This Dense's bias [fan_out]: a view into the flat parameter vector."""
+    return flat[self.bias_off:self.bias_off + self.fan_out]
 
 
 class MLPPlan:
@@ -648,7 +661,7 @@ class Model:
         ops.pack_weights(flat_params, p.pack_descs_ipe_dev, len(p.pack_descs_ipe), p.K * p.trunk[0][0].fan_out, p.wbf)
       if p.has_rgb:
         for (d, c0) in p.head_segs:
-          p.head_bias[c0:c0 + d.fan_out].copy_(flat_params[d.bias_off:d.bias_off + d.fan_out])
+          p.head_bias[c0:c0 + d.fan_out].copy_(d.bias(flat_params))
 
   # Parameters ------------------------------------------------------------------------
 
@@ -790,8 +803,7 @@ class Model:
     Lg = self.num_levels - 1
     if not (keep_for_backward and _MERGE_PROPS and Lg >= 2 and not self.single_mlp and self.stop_level_grad):
       return 0                                         # (stop_level_grad = False: the levels' backward passes run one after the other)
-    plan = self.prop_plan
-    return Lg if (self._chain_ok(plan) and not plan.has_rgb) else 0
+    return Lg if self._route(self.prop_plan, 0, keep_for_backward).chain else 0      # (M: the chain routes do not depend on it)
 
   # ------------------------------------------------------------------ forward
 
@@ -921,9 +933,9 @@ class Model:
       M = Bp * n
       tag = ('lvl', i_level) if keep_for_backward else ('lvl', 'shared', is_prop)
       group = (i_level, n_group) if (is_prop and n_group) else None
-      ipe_in_chain = fused_ipe and self._ipe_chain_ok(plan)
+      route = self._route(plan, M, keep_for_backward)
       feat = None
-      if not ipe_in_chain:
+      if not route.ipe:
         feat = self._lvl_buf(tag, 'feat', M, (plan.ldF,), bf16, group)
         ops.cast_rays_ipe(tdist, R.origins, R.directions, radii, plan.basis_dev, ray_shape=self.ray_shape,
                           warp_contract=(hp.warp_fn == 'contract'), min_deg=hp.min_deg_point,
@@ -943,10 +955,10 @@ class Model:
         if bw_ != bw_t:                                             # padded bottleneck columns (they feed zero kernel rows): no noise
           bnoise = torch.cat([bnoise, bnoise.new_zeros((M, bw_ - bw_t))], 1)
         bnoise = bnoise.contiguous()
-      if ipe_in_chain:
-        mlp_out = self._chain_forward_ipe(plan, flat, tdist, R, radii, M, tag)
+      if route.ipe:
+        mlp_out = self._chain_forward_ipe(plan, route, flat, tdist, R, radii, M, tag)
       else:
-        mlp_out = self._mlp_forward(plan, flat, feat, M, n, R, tag, keep_for_backward, tdist=tdist, bnoise=bnoise,
+        mlp_out = self._mlp_forward(plan, route, flat, feat, M, n, R, tag, keep_for_backward, tdist=tdist, bnoise=bnoise,
                                     group=group)
 
       # --- density noise (models.py:462-464), background colour (:241-254)
@@ -1043,6 +1055,21 @@ class Model:
     """A [rows, ld] view into the packed bf16 operand buffer."""
     return plan.wbf[off:off + rows * ld].view(rows, ld)
 
+  def _fw(self, plan, key):
+    """The forward image Bt [n_pad, K padded] of the packed entry `key` (`_layout_packed`)."""
+    e = plan.packed[key]
+    return self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])
+
+  def _bw(self, plan, key):
+    """The backward image [W, out padded] of the packed entry `key`, ('trunk', i) with i >= 1 or 'head': the operand of the dX
+    GEMM into the trunk layer below it."""
+    W, e = plan.W, plan.packed[key]
+    return self._w(plan, e['b_off'], _rup(W, 128), e['b_ld'])
+
+  def _chain_bws(self, plan):
+    """The backward images of a trunk as mnr_mlp_chain_bwd takes them: one per layer, None for layer 0 (nothing below it)."""
+    return [None] + [self._bw(plan, ('trunk', i)) for i in range(1, len(plan.trunk))]
+
   def _chain_ok(self, plan: MLPPlan):
     """The fused per-level kernels (csrc/fused_mlp.hip) cover a trunk of width 128 / 256, depth <= 8, with at most one
     skip concat: the proposal MLP of every config (with its Dense(1) head inside the kernel) and the 256-wide NeRF
@@ -1064,61 +1091,70 @@ class Model:
     W, D = plan.W, len(plan.trunk)
     acts = [self._buf((tag, 'act', i if keep else i % 2), (M, W), bf16) if (keep or i == D - 1) else None for i in range(D)]
     bits = [self._buf((tag, 'bits', i), (M, W // 8), torch.uint8) if need_bits else None for i in range(D)]
-    layers, skip = [], 0
-    for i, (d, concat) in enumerate(plan.trunk):
-      e = plan.packed[('trunk', i)]
-      layers.append((self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), flat[d.bias_off:d.bias_off + d.fan_out]))
-      if concat:
-        skip = i
+    layers, skip, _ = self._chain_layers(plan, flat)
     ops.mlp_chain_fwd(feat, plan.ldF, layers, M=M, W=W, acts=acts, bits=bits if need_bits else None, skip_layer=skip)
     return acts, bits
 
-  def _chain_forward(self, plan: MLPPlan, flat, feat, M, tag, keep, group=None):
+  def _chain_layers(self, plan: MLPPlan, flat, ipe=False, head=False):
+    """The fused chain's operands -> (layers = [(Bt, bias)] per trunk layer, the skip layer's index (0: none), head).  `ipe`:
+    layer 0's group-major image 'trunk0_ipe' (which only a trunk without a skip concat has: `_ipe_chain_ok`).  `head`: the
+    density head's keywords dict(w_head, b_head) for the launch, else {}."""
+    layers, skip = [], 0
+    for i, (d, concat) in enumerate(plan.trunk):
+      layers.append((self._fw(plan, 'trunk0_ipe' if (ipe and i == 0) else ('trunk', i)), d.bias(flat)))
+      if concat:
+        skip = i
+    return layers, skip, (dict(w_head=self._fw(plan, 'density')[0], b_head=plan.density.bias(flat)) if head else {})
+
+  @staticmethod
+  def _mlp_result(route: Route, **kw):
+    """What an MLP forward returns: its tensors and the route it took ('route': what the backward pass reads).  Which storage the
+    level ended up in also under 'chain' / 'chain_trunk' / 'panel', the names tests/test_gpu_chain.py and tests/test_sim_model.py
+    assert on."""
+    return dict(route=route, chain=route.chain, chain_trunk=route.chain_trunk, panel=route.panel, **kw)
+
+  def _chain_forward(self, plan: MLPPlan, route, flat, feat, M, tag, keep, group=None):
     """models.py:441-465 for a density-only MLP as ONE launch: every Dense + ReLU layer and the density head."""
     W, D = plan.W, len(plan.trunk)
     acts = [self._lvl_buf(tag, ('act', i), M, (W,), bf16, group) for i in range(D)] if keep else None
     bits = [self._lvl_buf(tag, ('bits', i), M, (W // 8,), torch.uint8, group) for i in range(D)] if keep else None
-    layers, skip = [], 0
-    for i, (d, concat) in enumerate(plan.trunk):
-      e = plan.packed[('trunk', i)]
-      layers.append((self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), flat[d.bias_off:d.bias_off + d.fan_out]))
-      if concat:
-        skip = i
-    e = plan.packed['density']
-    d = plan.density
+    layers, skip, head = self._chain_layers(plan, flat, head=True)
     raw_density = self._buf((tag, 'raw_density'), (M,), f32)
-    ops.mlp_chain_fwd(feat, plan.ldF, layers, M=M, W=W, w_head=self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])[0],
-                      b_head=flat[d.bias_off:d.bias_off + 1], head_out=raw_density, acts=acts, bits=bits,
-                      skip_layer=skip)
-    return dict(acts=acts or [], bits=bits or [], raw_density=raw_density, chain=True)
+    ops.mlp_chain_fwd(feat, plan.ldF, layers, M=M, W=W, **head, head_out=raw_density, acts=acts, bits=bits, skip_layer=skip)
+    return self._mlp_result(route, acts=acts or [], bits=bits or [], raw_density=raw_density)
 
   def _ipe_chain_ok(self, plan: MLPPlan):
     """A density-only MLP on the fused chain without a skip concat (the proposal MLP of every BASELINE config), with an
     encoding the in-kernel producer covers (groups of four degrees, at most 24 basis directions)."""
     return self._chain_ok(plan) and 'trunk0_ipe' in plan.packed
 
-  def _chain_forward_ipe(self, plan: MLPPlan, flat, tdist, R, radii, M, tag):
+  def _chain_forward_ipe(self, plan: MLPPlan, route, flat, tdist, R, radii, M, tag):
     """models.py:441-465 for a density-only MLP AND its featurisation (render.cast_rays + integrated_pos_enc,
     models.py:413-431) as ONE launch; inference only (nothing is kept for a backward pass)."""
     hp, W = plan.hp, plan.W
-    layers = []
-    for i, (d, _) in enumerate(plan.trunk):
-      e = plan.packed['trunk0_ipe' if i == 0 else ('trunk', i)]
-      layers.append((self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), flat[d.bias_off:d.bias_off + d.fan_out]))
-    e = plan.packed['density']
-    d = plan.density
+    layers, _, head = self._chain_layers(plan, flat, ipe=True, head=True)
     raw_density = self._buf((tag, 'raw_density'), (M,), f32)
     ops.mlp_chain_fwd_ipe(tdist, R.origins, R.directions, radii, plan.basis_dev, layers, M=M, W=W, ray_shape=self.ray_shape,
                           warp_contract=(hp.warp_fn == 'contract'), min_deg=hp.min_deg_point, max_deg=hp.max_deg_point,
-                          disable_integration=self.disable_integration,
-                          w_head=self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])[0], b_head=flat[d.bias_off:d.bias_off + 1],
-                          head_out=raw_density)
-    return dict(acts=[], bits=[], raw_density=raw_density, chain=True)
+                          disable_integration=self.disable_integration, **head, head_out=raw_density)
+    return self._mlp_result(route, acts=[], bits=[], raw_density=raw_density)
 
-  def _tangent_forward(self, plan: MLPPlan, tdist, R, M, bits, keep, tag, zs=None, T_feat=None):
+  def _dense_fwd(self, x, x2, Bt, dst, M, act=None, out=None, **kw):
+    """One Dense layer as its GEMM: dst [M, width] = epilogue([x | x2] Bt^T) over all (padded) columns of x and of x2, the
+    skip-concat input or None.  `kw`: what the site asks of the epilogue and the layouts (bias, ReLU, mask bits, panel storage,
+    walk order).  A non-ReLU net_activation `act`: the GEMM stores the pre-activation in dst, a second kernel applies softplus /
+    silu into `out`."""
+    width = dst.shape[1]
+    cat = dict(A2=x2, K2=x2.shape[1]) if x2 is not None else {}
+    ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=x.shape[1], **cat, Cb=dst, ldcb=width, nb=width, **kw)
+    if act is not None:
+      ops.act_fwd(act, dst, out)
+
+  def _tangent_forward(self, plan: MLPPlan, route, tdist, R, M, bits, keep, tag, zs=None, T_feat=None):
     """Density-gradient normals by forward mode (models.py:473-492 without a second autodiff pass): the three
     tangent feature rows d features / d mean_c of every sample run through the trunk as 3 * M extra GEMM rows whose ReLU is the
-    primal layer's 1-bit mask; the density column of the last layer gives raw_grad [3, M]."""
+    primal layer's 1-bit mask; the density column of the last layer gives raw_grad [3, M].  -> (T_feat, T_acts, raw_grad, T_pre),
+    T_pre the tangent pre-activations of a non-ReLU net (for `_tangent_backward`)."""
     hp = plan.hp
     if T_feat is None:                                    # (given: pre-built tangent rows [3 M, ldF], `mlp_call`)
       T_feat = self._buf((tag, 'T_feat'), (3 * M, plan.ldF), bf16)
@@ -1131,11 +1167,10 @@ class Model:
     relu = hp.net_activation == 'relu'
     D = len(plan.trunk)
     # (training only: the chain writes every layer's rows, which the weight-gradient GEMMs want anyway; inference ping-pongs two buffers)
-    chain = bool(_TANGENT_CHAIN and keep and relu and self._chain_ok(plan) and all(b is not None for b in bits))
+    chain = bool(_TANGENT_CHAIN and keep and relu and route.fused and all(b is not None for b in bits))
     i = 0
     while i < D:
-      d, concat = plan.trunk[i]
-      e2 = plan.packed[('trunk', i)]
+      concat = plan.trunk[i][1]
       run = 0
       if chain and i >= 1 and not concat:
         while i + run < D and not plan.trunk[i + run][1]:
@@ -1148,8 +1183,7 @@ class Model:
         Bws, cbits = [None] * (run + 1), [None] * (run + 1)
         for j in range(1, run + 1):
           l = i + run - j
-          el = plan.packed[('trunk', l)]
-          Bws[j] = self._w(plan, el['f_off'], el['n_pad'], el['f_ld'])[:plan.W]
+          Bws[j] = self._fw(plan, ('trunk', l))[:plan.W]
           cbits[j - 1] = bits[l]
         cbits[run] = bits[i]                                  # (unused with dY_in; the launcher wants a pointer)
         for c in range(3):
@@ -1161,17 +1195,11 @@ class Model:
         i += run
         continue
       tout = self._buf((tag, 'T_act', i if keep else i % 2), (3 * M, plan.W), bf16)
-      Bt2 = self._w(plan, e2['f_off'], e2['n_pad'], e2['f_ld'])
       # ReLU: T_i = mask_i * (T_{i-1} W_i), the mask applied in the GEMM's epilogue.  Any other activation: the GEMM leaves the
       # tangent pre-activation U_i (kept for the backward pass's act'' term), then T_i = act'(z_i) * U_i
       mk = dict(bits_in=bits[i], bits_row_mod=M) if relu else {}
       dst = tout if relu else self._buf((tag, 'T_pre', i if keep else i % 2), (3 * M, plan.W), bf16)
-      if i == 0:
-        ops.gemm_nt(T_feat, Bt2, M=3 * M, N=e2['n_pad'], K1=plan.ldF, Cb=dst, ldcb=plan.W, nb=plan.W, **mk)
-      elif concat:
-        ops.gemm_nt(t, Bt2, M=3 * M, N=e2['n_pad'], K1=plan.W, A2=T_feat, K2=plan.ldF, Cb=dst, ldcb=plan.W, nb=plan.W, **mk)
-      else:
-        ops.gemm_nt(t, Bt2, M=3 * M, N=e2['n_pad'], K1=plan.W, Cb=dst, ldcb=plan.W, nb=plan.W, **mk)
+      self._dense_fwd(T_feat if i == 0 else t, T_feat if concat else None, self._fw(plan, ('trunk', i)), dst, 3 * M, **mk)
       if not relu:
         ops.act_tangent_fwd(hp.net_activation, zs[i], dst, tout)
         T_pre.append(dst)
@@ -1179,27 +1207,27 @@ class Model:
       t = tout
       i += 1
     raw_grad = self._buf((tag, 'raw_grad'), (3, M), f32)
-    ed = plan.packed['density']
-    ops.gemm_nt(t, self._w(plan, ed['f_off'], ed['n_pad'], ed['f_ld']), M=3 * M, N=ed['n_pad'], K1=plan.W,
-                Cf=raw_grad, ldcf=1, f0=0, nf=1)
-    self._T_pre = T_pre                                   # (non-ReLU activations: the tangent pre-activations, for _tangent_backward)
-    return T_feat, T_acts, raw_grad
+    Bd = self._fw(plan, 'density')
+    ops.gemm_nt(t, Bd, M=3 * M, N=Bd.shape[0], K1=plan.W, Cf=raw_grad, ldcf=1, f0=0, nf=1)
+    return T_feat, T_acts, raw_grad, T_pre
 
-  def _mlp_forward(self, plan: MLPPlan, flat, feat, M, n, R, tag, keep, tdist=None, bnoise=None, group=None, T_feat=None):
-    """MLP.__call__ (models.py:402-612) for the M = B*n samples of one level.  `T_feat`: pre-built tangent rows for the
-    density-gradient normals (`mlp_call`: the caller's Gaussians have no ray to cast); None = cast them from the rays."""
+  def _mlp_forward(self, plan: MLPPlan, route: Route, flat, feat, M, n, R, tag, keep, tdist=None, bnoise=None, group=None,
+                   T_feat=None):
+    """MLP.__call__ (models.py:402-612) for the M = B*n samples of one level on the route `_route(plan, M, keep)` gave.
+    `T_feat`: pre-built tangent rows for the density-gradient normals (`mlp_call`: the caller's Gaussians have no ray to cast);
+    None = cast them from the rays."""
     hp = plan.hp
-    chain = self._chain_ok(plan)
-    if chain and not plan.has_rgb:
-      return self._chain_forward(plan, flat, feat, M, tag, keep, group)
+    if route.chain:
+      return self._chain_forward(plan, route, flat, feat, M, tag, keep, group)
     assert group is None
     relu = hp.net_activation == 'relu'
-    need_bits = ((keep and _USE_BITS) or plan.tangent) and relu
+    act = None if relu else hp.net_activation
+    chain, need_bits = route.chain_trunk, route.need_bits
     acts, bits, zs, vzs = [], [], [], []
     x = None
     # panel layout for the trunk of this level (the layout of acts / bits / every trunk dY of the backward pass): every
     # producer and consumer is then a panel-aware GEMM, which the plain merged head of a wide ReLU trunk guarantees
-    panel = self._panel_ok(plan, M, keep)
+    panel = route.panel
     PAN = ops.LAYOUT_PANEL
     lay_c = dict(c_layout=PAN) if panel else {}
     lay_a = dict(a1_layout=PAN) if panel else {}
@@ -1214,36 +1242,24 @@ class Model:
       acts, bits = self._chain_trunk(plan, flat, feat, M, tag, keep, need_bits)
       x = acts[-1]
     for i, (d, concat) in enumerate([] if chain else plan.trunk):
-      e = plan.packed[('trunk', i)]
       out = self._buf((tag, 'act', i if keep else i % 2), (M, plan.W), bf16)
       # 1-bit ReLU mask: backward pass (training) and the tangent pass of the density-gradient normals
       bo = self._buf((tag, 'bits', i if (keep or plan.tangent) else i % 2), (M, plan.W // 8), torch.uint8) if need_bits else None
       bits.append(bo)
-      Bt = self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])
-      bias = flat[d.bias_off:d.bias_off + d.fan_out]
-      # non-ReLU activations: the GEMM stores the pre-activation, a second kernel applies softplus / silu
       dst = out if relu else activate((tag, 'z', i if (keep or plan.tangent) else i % 2), out, plan.W, zs)
-      if i == 0:
-        ops.gemm_nt(feat, Bt, M=M, N=e['n_pad'], K1=plan.ldF, bias=bias, n_bias=d.fan_out, relu=relu,
-                    Cb=dst, ldcb=plan.W, nb=plan.W, bits_out=bo, walk_descending=bool(i & 1), **lay_c)
-      elif concat:
-        ops.gemm_nt(x, Bt, M=M, N=e['n_pad'], K1=plan.W, A2=feat, K2=plan.ldF, bias=bias, n_bias=d.fan_out,
-                    relu=relu, Cb=dst, ldcb=plan.W, nb=plan.W, bits_out=bo, walk_descending=bool(i & 1), **lay_a, **lay_c)
-      else:
-        ops.gemm_nt(x, Bt, M=M, N=e['n_pad'], K1=plan.W, bias=bias, n_bias=d.fan_out, relu=relu,
-                    Cb=dst, ldcb=plan.W, nb=plan.W, bits_out=bo, walk_descending=bool(i & 1), **lay_a, **lay_c)
-      if not relu:
-        ops.act_fwd(hp.net_activation, dst, out)
+      # (layer 0 reads the row-major features; the layers above it the trunk's own layout)
+      self._dense_fwd(feat if i == 0 else x, feat if concat else None, self._fw(plan, ('trunk', i)), dst, M, act, out,
+                      bias=d.bias(flat), n_bias=d.fan_out, relu=relu, bits_out=bo, walk_descending=bool(i & 1),
+                      **({} if i == 0 else lay_a), **lay_c)
       acts.append(out)
       x = out
-    res = dict(acts=acts, bits=bits, chain_trunk=chain, zs=zs, vzs=vzs, panel=panel)
+    res = self._mlp_result(route, acts=acts, bits=bits, zs=zs, vzs=vzs)
     raw_density = self._buf((tag, 'raw_density'), (M,), f32)
     if plan.has_rgb and not plan.use_viewdirs:
       # models.py:585 with x = the trunk output: one 4-column head [raw_density | raw_rgb] as an fp32 side output
-      e = plan.packed['head4']
+      Bt = self._fw(plan, 'head4')
       small4 = self._buf((tag, 'small4'), (M, 4), f32)
-      ops.gemm_nt(x, self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), M=M, N=e['n_pad'], K1=plan.W, bias=plan.head_bias,
-                  n_bias=4, relu=False, Cf=small4, ldcf=4, f0=0, nf=4)
+      ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.head_bias, n_bias=4, relu=False, Cf=small4, ldcf=4, f0=0, nf=4)
       raw_density.copy_(small4[:, 0])
       raw_rgb = self._buf((tag, 'raw_rgb'), (M, 3), f32)
       raw_rgb.copy_(small4[:, 1:4])
@@ -1251,30 +1267,30 @@ class Model:
       return res
     if plan.has_rgb:
       bw = hp.bottleneck_width
-      e = plan.packed['head']
       VI = self._buf((tag, 'VI'), (M, plan.ldVI), bf16)
-      Bt = self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])
+      Bt = self._fw(plan, 'head')
+      nh = Bt.shape[0]
       if plan.ref:
         small = self._buf((tag, 'small'), (M, 11), f32)
-        ops.gemm_nt(x, Bt, M=M, N=e['n_pad'], K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
+        ops.gemm_nt(x, Bt, M=M, N=nh, K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
                     Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=small, ldcf=11, f0=bw, nf=11)
         raw_density.copy_(small[:, 0])
         raw_grad = None
         if plan.tangent:
-          T_feat, T_acts, raw_grad = self._tangent_forward(plan, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
-          res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, T_pre=self._T_pre)
+          T_feat, T_acts, raw_grad, T_pre = self._tangent_forward(plan, route, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
+          res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, T_pre=T_pre)
         normals, npred, rough = ops.ref_head_fwd(small, raw_grad, R.viewdirs, n, plan.ide, hp.roughness_bias, VI,
                                                  bw, plan.ldVI, features=plan.features, deg_view=hp.deg_view)
         res.update(small=small, normals=normals, npred=npred, rough=rough)
       elif plan.pn:
         # [raw_density | grad_pred] as the fp32 side output; normals_pred = -l2_normalize(grad_pred) (models.py:494-503)
         small = self._buf((tag, 'small_pn'), (M, 4), f32)
-        ops.gemm_nt(x, Bt, M=M, N=e['n_pad'], K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
+        ops.gemm_nt(x, Bt, M=M, N=nh, K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
                     Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=small, ldcf=4, f0=bw, nf=4, **lay_a)
         raw_density.copy_(small[:, 0])
         ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
         res.update(small=small, npred=ops.pred_normals_fwd(small, 1))
-      elif panel and _HEAD_VCOL and bw == 256 and plan.W <= 1536:
+      elif route.vcol:
         # the plain merged head [bottleneck | density] behind a panel-storage trunk: N = 256 and the density column as a VECTOR
         # (row bw of the merged forward image) instead of a second 256-column tile for one column (mnr_gemm_nt_args.vcol:
         # one extra MFMA per wave and k-step; bitwise the merged operand's result)
@@ -1282,14 +1298,14 @@ class Model:
                     vcol=Bt[bw], vcol_out=raw_density, vcol_bias=plan.head_bias[bw:bw + 1], **lay_a)
         ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
       else:
-        ops.gemm_nt(x, Bt, M=M, N=e['n_pad'], K1=plan.W, bias=plan.head_bias, n_bias=bw + 1, relu=False,
+        ops.gemm_nt(x, Bt, M=M, N=nh, K1=plan.W, bias=plan.head_bias, n_bias=bw + 1, relu=False,
                     Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=raw_density, ldcf=1, f0=bw, nf=1, **lay_a)
         ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
       if plan.dn:
         # density-gradient normals without the rest of the Ref-NeRF head (models.py:478-492): for the renderings and the
         # orientation loss; they do not enter the colour
-        T_feat, T_acts, raw_grad = self._tangent_forward(plan, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
-        res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, normals=ops.density_normals_fwd(raw_grad), T_pre=self._T_pre)
+        T_feat, T_acts, raw_grad, T_pre = self._tangent_forward(plan, route, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
+        res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, normals=ops.density_normals_fwd(raw_grad), T_pre=T_pre)
       if plan.glo > 0:
         # (`mlp_call` feeds the caller's glo_vec as a table of its own, one row per ray)
         glo_table = getattr(R, 'glo_table', None)
@@ -1301,29 +1317,16 @@ class Model:
       vacts, vbits = [], []
       WV = hp.net_width_viewdirs
       for i, (d, concat) in enumerate(plan.view):
-        e = plan.packed[('view', i)]
         out = self._buf((tag, 'vact', i if keep else i % 2), (M, WV), bf16)
-        Bt = self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])
-        bias = flat[d.bias_off:d.bias_off + d.fan_out]
         dst = out if relu else activate((tag, 'vz', i if keep else i % 2), out, WV, vzs)
-        if i == 0:
-          ops.gemm_nt(VI, Bt, M=M, N=e['n_pad'], K1=plan.ldVI, bias=bias, n_bias=d.fan_out, relu=relu,
-                      Cb=dst, ldcb=WV, nb=WV)
-        elif concat:
-          ops.gemm_nt(h, Bt, M=M, N=e['n_pad'], K1=WV, A2=VI, K2=plan.ldVI, bias=bias, n_bias=d.fan_out,
-                      relu=relu, Cb=dst, ldcb=WV, nb=WV)
-        else:
-          ops.gemm_nt(h, Bt, M=M, N=e['n_pad'], K1=WV, bias=bias, n_bias=d.fan_out, relu=relu,
-                      Cb=dst, ldcb=WV, nb=WV)
-        if not relu:
-          ops.act_fwd(hp.net_activation, dst, out)
+        self._dense_fwd(h, VI if concat else None, self._fw(plan, ('view', i)), dst, M, act, out, bias=d.bias(flat),
+                        n_bias=d.fan_out, relu=relu)
         vacts.append(out)
         h = out
-      e = plan.packed['rgb']
       raw_rgb = self._buf((tag, 'raw_rgb'), (M, 3), f32)
-      d = plan.rgb
-      ops.gemm_nt(h, self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), M=M, N=e['n_pad'], K1=e['kpad'],
-                  bias=flat[d.bias_off:d.bias_off + 3], n_bias=3, relu=False, Cf=raw_rgb, ldcf=3, f0=0, nf=3)
+      Bt = self._fw(plan, 'rgb')
+      ops.gemm_nt(h, Bt, M=M, N=Bt.shape[0], K1=Bt.shape[1], bias=plan.rgb.bias(flat), n_bias=3, relu=False, Cf=raw_rgb, ldcf=3,
+                  f0=0, nf=3)
       res.update(VI=VI, vacts=vacts, raw_rgb=raw_rgb)
       if plan.diffuse_on:
         # models.py:584-602: tinted (or halved) specular + diffuse, tone-mapped; compositing then sees final colours
@@ -1331,10 +1334,9 @@ class Model:
         res['raw_rgb'] = ops.ref_color_fwd(raw_rgb, res['small'], hp.rgb_premultiplier, hp.rgb_bias, hp.rgb_padding,
                                            hp.use_specular_tint)
     else:
-      e = plan.packed['density']
-      d = plan.density
-      ops.gemm_nt(x, self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), M=M, N=e['n_pad'], K1=plan.W,
-                  bias=flat[d.bias_off:d.bias_off + 1], n_bias=1, relu=False, Cf=raw_density, ldcf=1, f0=0, nf=1)
+      Bt = self._fw(plan, 'density')
+      ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.density.bias(flat), n_bias=1, relu=False, Cf=raw_density, ldcf=1,
+                  f0=0, nf=1)
     res['raw_density'] = raw_density
     return res
 
@@ -1360,6 +1362,27 @@ class Model:
       return False
     return (not keep) or self._head_gcol(plan)
 
+  def _route(self, plan: MLPPlan, M, keep) -> Route:
+    """The route of `plan` for a level of M rows, `keep`: with a backward pass to follow.  Read from the module switches per call
+    (tests and bench.py set them between calls): nothing here is cached on the model or the plan."""
+    chain = self._chain_ok(plan)
+    panel = self._panel_ok(plan, M, keep)
+    relu = plan.hp.net_activation == 'relu'
+    return Route(chain=chain and not plan.has_rgb, chain_trunk=chain and plan.has_rgb,
+                 ipe=bool(_FUSED_IPE and not keep and self._ipe_chain_ok(plan)), panel=panel,
+                 # (a panel trunk's head is the plain merged head [bottleneck | density]: `_panel_ok`)
+                 vcol=bool(panel and _HEAD_VCOL and plan.hp.bottleneck_width == 256 and plan.W <= 1536),
+                 gcol=self._head_gcol(plan), need_bits=bool(((keep and _USE_BITS) or plan.tangent) and relu))
+
+  def _rank1_last(self, plan: MLPPlan, feature_gradient):
+    """Whether the last hidden layer's dY = relu'(z) * (g (x) w_density) of a Dense(1)-headed chain (the proposal MLP, reference
+    models.py:457-460) can stay unstored: its weight-gradient GEMM then builds it from the factors (`mnr_gemm_tn_args.rank1_*`).  Not
+    when another reader needs the matrix (a skip concat's second GEMM, the feature gradient of a one-layer trunk)."""
+    W, D = plan.W, len(plan.trunk)
+    concat_last = bool(plan.trunk[D - 1][1])
+    k_in = plan.ldF if D == 1 else W
+    return bool(_RANK1_LAST and W % 256 == 0 and k_in % 256 == 0 and not concat_last and not (feature_gradient and D == 1))
+
   def _glo_table(self, flat):
     G = self.num_glo_features
     return flat[self.glo_off:self.glo_off + self.num_glo_embeddings * G].view(self.num_glo_embeddings, G)
@@ -1374,8 +1397,8 @@ class Model:
     unused, as in the reference.  rng None: deterministic; a torch.Generator or a seed draws density_noise / bottleneck_noise
     as `_forward` does; noise = {'density_noise': [..., n] (or one value), 'bottleneck_noise': [..., n, bottleneck]} overrides
     the draw.  Inference only: nothing is kept for a backward pass, and the activation buffers are the call's own
-    (('mlpcall', module)), so a call between a training forward pass and its backward pass touches no ('lvl', ...) buffer,
-    `_saved` or `_T_pre`.  PRECONDITION for such a call: the bound parameters are the tensor that forward pass ran on (what
+    (('mlpcall', module)), so a call between a training forward pass and its backward pass touches no ('lvl', ...) buffer
+    and not `_saved`.  PRECONDITION for such a call: the bound parameters are the tensor that forward pass ran on (what
     construct_model + train_utils give: the parameters are updated in place).  The call re-packs the bound parameters into
     the shared operand images (`pack_weights`: every plan's wbf / head_bias) and, for padded trunk widths, into the shared
     execution-layout vector (`_to_exec`), both of which a pending backward pass reads; after
@@ -1442,7 +1465,8 @@ class Model:
     # A density-only MLP on the fused chain is evaluated by Model.__call__ without a backward pass (render / eval) with layer
     # 0's K walked group-major (mnr_mlp_chain_fwd_ipe, `_chain_forward_ipe`); the call takes the same form, so that it returns
     # what such a pass returns, bit for bit (`_chain_forward_grouped`)
-    grouped = bool(_FUSED_IPE and self._ipe_chain_ok(plan))
+    route = self._route(plan, Mp, False)
+    grouped = route.ipe
     self.pack_weights(flat, ipe=grouped)
 
     nz = noise or {}
@@ -1485,20 +1509,19 @@ class Model:
 
     R = types.SimpleNamespace(viewdirs=vd, radii=None, origins=None, directions=None, glo_table=glo_tab)
     missing = object()
-    keep_cam, keep_tpre = getattr(self, '_glo_cam', missing), getattr(self, '_T_pre', missing)
+    keep_cam = getattr(self, '_glo_cam', missing)
     try:
       if glo_tab is not None:
         self._glo_cam = self._const(('mlpcall', 'glo_idx'), (Mp,), lambda: torch.arange(Mp, dtype=torch.int32, device=dev))
       if grouped:
-        out = self._chain_forward_grouped(plan, flat, feat, Mp, tag)
+        out = self._chain_forward_grouped(plan, route, flat, feat, Mp, tag)
       else:
-        out = self._mlp_forward(plan, flat, feat, Mp, 1, R, tag, False, bnoise=bnoise, T_feat=T_feat)
+        out = self._mlp_forward(plan, route, flat, feat, Mp, 1, R, tag, False, bnoise=bnoise, T_feat=T_feat)
     finally:
-      for name, val in (('_glo_cam', keep_cam), ('_T_pre', keep_tpre)):
-        if val is missing:
-          self.__dict__.pop(name, None)
-        else:
-          setattr(self, name, val)
+      if keep_cam is missing:
+        self.__dict__.pop('_glo_cam', None)
+      else:
+        self._glo_cam = keep_cam
 
     # density = act(raw + noise + bias), colour = act(premultiplier * raw + bias) padded (models.py:506,584-602): per sample
     # inside mnr_composite_fwd, the kernel the level loop takes both from; its step function here is a dummy (32 samples per row
@@ -1534,7 +1557,7 @@ class Model:
         normals_pred=shaped(out['npred'], 3) if hp.enable_pred_normals else None,
         roughness=shaped(out['rough'], 1) if out.get('rough') is not None else None)
 
-  def _chain_forward_grouped(self, plan: MLPPlan, flat, feat, M, tag):
+  def _chain_forward_grouped(self, plan: MLPPlan, route, flat, feat, M, tag):
     """`_chain_forward_ipe` for a feature matrix that already exists (`mlp_call`): the rows' columns are moved into the
     group-major order of the in-kernel producer (four degrees per group of MNR_CHAIN_IPE_GROUP_COLS columns, the rest zero;
     a copy, no arithmetic) and mnr_mlp_chain_fwd runs on layer 0's group-major image 'trunk0_ipe'.  Same bf16 features, same
@@ -1551,16 +1574,10 @@ class Model:
     src, dst = self._const(('mlpcall', 'group_perm', plan.module_name), (K, Ld, G), perm)
     feat_g = self._buf((tag, 'feat_g'), (M, ld_g), bf16, zero=True)          # (the columns outside `dst` stay zero)
     feat_g.index_copy_(1, dst, feat.index_select(1, src))
-    layers = []
-    for i, (d, _) in enumerate(plan.trunk):
-      e = plan.packed['trunk0_ipe' if i == 0 else ('trunk', i)]
-      layers.append((self._w(plan, e['f_off'], e['n_pad'], e['f_ld']), flat[d.bias_off:d.bias_off + d.fan_out]))
-    e = plan.packed['density']
-    d = plan.density
+    layers, _, head = self._chain_layers(plan, flat, ipe=True, head=True)
     raw_density = self._buf((tag, 'raw_density'), (M,), f32)
-    ops.mlp_chain_fwd(feat_g, ld_g, layers, M=M, W=W, w_head=self._w(plan, e['f_off'], e['n_pad'], e['f_ld'])[0],
-                      b_head=flat[d.bias_off:d.bias_off + 1], head_out=raw_density)
-    return dict(acts=[], bits=[], raw_density=raw_density, chain=True)
+    ops.mlp_chain_fwd(feat_g, ld_g, layers, M=M, W=W, **head, head_out=raw_density)
+    return self._mlp_result(route, acts=[], bits=[], raw_density=raw_density)
 
   def query_density(self, xyz, std=0.0):
     """The NeRF level's density at the points xyz [..., 3] (isotropic Gaussians of standard deviation `std`): the query a
@@ -1573,6 +1590,30 @@ class Model:
     vd = torch.tensor([0., 0., 1.], dtype=f32, device=dev).expand(lead + (3,)).contiguous() if plan.use_viewdirs else None
     glo = torch.zeros(lead + (plan.glo,), dtype=f32, device=dev) if plan.glo > 0 else None
     return self.mlp_call(plan, None, gaussians, viewdirs=vd, glo_vec=glo)['density']
+
+  def _trunk_dw(self, plan: MLPPlan, grads, i, acts, feat, dY, M, bias=True, rank1=None, panel=False, **kw):
+    """Weight gradient of trunk layer i from its output gradient dY [M, W]: dW_i += [x_{i-1} | feat]^T dY (layer 0: feat^T dY;
+    the feature rows of a skip layer as a second GEMM), and db_i += the column sums of dY in the first launch unless `bias` is
+    off (the tangent network has none).  acts / feat: the trunk's activations and features (the tangent network's: T_acts, T_feat).
+    rank1: dY is None and the GEMM builds it from these factors (`_rank1_last`).  panel: acts and dY are in panel storage (the
+    features never are).  `kw` (m_interleave, max_wgs) goes to the first launch.  k_valid / n_valid are written out for every
+    segment: for an activation segment they are K and N, what the launcher fills in when it is given none."""
+    d, concat = plan.trunk[i]
+    W, F, ldF, PAN = plan.W, plan.F, plan.ldF, ops.LAYOUT_PANEL
+    tn_b = dict(b_layout=PAN) if panel else {}
+    x, ldx, kx, tn_a = (feat, ldF, F, {}) if i == 0 else (acts[i - 1], W, W, dict(a_layout=PAN) if panel else {})
+    db = dict(bias_out=grads[d.bias_off:d.bias_off + W], bias_n_valid=W) if bias else {}
+    ops.gemm_tn(x, dY, grads[d.kernel_off:d.kernel_off + kx * W], M=M, K=ldx, N=W, lda=ldx, ldb=W, ldc=W, k_valid=kx, n_valid=W,
+                rank1=rank1, **db, **tn_a, **tn_b, **kw)
+    if concat:
+      o = d.kernel_off + W * W
+      ops.gemm_tn(feat, dY, grads[o:o + F * W], M=M, K=ldF, N=W, lda=ldF, ldb=W, ldc=W, k_valid=F, n_valid=W, **tn_b)
+
+  def _trunk_dx(self, plan: MLPPlan, i, dY, out, M, **kw):
+    """Input gradient of trunk layer i >= 1: out [M, W] = epilogue(dY @ kernel_i[:W]^T), the gradient of layer i - 1's output.
+    `kw`: that layer's ReLU mask, the layouts, the walk order, the workgroup cap."""
+    Bw = self._bw(plan, ('trunk', i))
+    ops.gemm_nt(dY, Bw, M=M, N=Bw.shape[0], K1=Bw.shape[1], Cb=out, ldcb=plan.W, nb=plan.W, **kw)
 
   @_in_library
   def backward_level(self, lv, flat, grads, g_rgb_out, g_weights, g_expo=None, g_normals=None, g_npred=None, losses=None,
@@ -1590,6 +1631,7 @@ class Model:
     M, n, tag = lv['M'], lv['n'], lv['tag']
     R = self._saved['rays']
     mlp = lv['mlp']
+    route: Route = mlp['route']
     acts = mlp['acts']
     x_last = acts[-1]
     W = plan.W
@@ -1607,19 +1649,18 @@ class Model:
     def dv_buf(i, nv):
       return self._buf(('bwd', slot, 'dV0' if (nv - 1 - i) % 2 == 0 else 'dV1', WV), (M, WV), bf16)
 
-    if not mlp.get('chain'):
+    if not route.chain:
       dA = dy_buf(D - 1)
 
     def gslice(off, size):
       return grads[off:off + size]
 
     relu = hp.net_activation == 'relu'
-    panel = bool(mlp.get('panel'))                        # the trunk's activations / masks / gradients are in panel storage
+    panel = route.panel                                   # the trunk's activations / masks / gradients are in panel storage
     PAN = ops.LAYOUT_PANEL
     lay_c = dict(c_layout=PAN) if panel else {}
     lay_ac = dict(a1_layout=PAN, c_layout=PAN) if panel else {}
     tn_a = dict(a_layout=PAN) if panel else {}
-    tn_b = dict(b_layout=PAN) if panel else {}
 
     def act_vjp(z, d):
       """Non-ReLU activations: d (gradient w.r.t. a layer's activation, just written without a mask) *= act'(z)."""
@@ -1676,7 +1717,7 @@ class Model:
       # dW GEMM as a vector, below; it then also leaves the compositing VJP as the fp32 vector that GEMM reads)
       # (for trunks of at least 512 columns: at 256 the merged N = 384 GEMM is six small tiles and the extra column buys nothing,
       # blender_256 1.764 / 1.767 M rays/s merged against 1.749 / 1.764 M, llff_raw 546.0 against 545.9 k)
-      head_gcol = self._head_gcol(plan)
+      head_gcol = route.gcol
       assert head_gcol or not panel
       g_den_f32, g_rgb = ops.composite_bwd(
           lv['ccfg'], lv['raw_density'], lv['tdist'], R.directions, lv['weights'], raw_rgb=lv['raw_rgb'],
@@ -1775,7 +1816,6 @@ class Model:
                                       dVIa, dVIb, bw, g_npred, g_normals, dHB, bw + 1, bw + 10, features=plan.features,
                                       deg_view=hp.deg_view)
       # merged head: dW, db, dX_last
-      e = plan.packed['head']
       if head_gcol:
         # dW_bottleneck += x^T dHB[:, :bw] straight into the flat gradient (256x256 tiles), dw_density += x^T g as one more
         # column of the same launch (db_density: above)
@@ -1792,39 +1832,30 @@ class Model:
         for (d, c0) in plan.head_segs:
           ops.scatter_add(tmpW, nh, 0, c0, W, d.fan_out, gslice(d.kernel_off, W * d.fan_out), d.fan_out)
           ops.scatter_add(tmpb, nh, 0, c0, 1, d.fan_out, gslice(d.bias_off, d.fan_out), d.fan_out)
-      Bw = self._w(plan, e['b_off'], _rup(W, 128), e['b_ld'])
       # (K = the head's columns rounded to the GEMM's 64-column K granule, not to the buffers' 128: 320 instead of 384 at 360.gin)
-      ops.gemm_nt(dHB, Bw, M=M, N=_rup(W, 128), K1=_rup(plan.head_cols, 32 if (panel and _HEAD_K32) else 64), Cb=dA, ldcb=W, nb=W,
-                  **mask_kw(len(acts) - 1), **lay_c)
+      ops.gemm_nt(dHB, self._bw(plan, 'head'), M=M, N=_rup(W, 128), K1=_rup(plan.head_cols, 32 if (panel and _HEAD_K32) else 64),
+                  Cb=dA, ldcb=W, nb=W, **mask_kw(len(acts) - 1), **lay_c)
       act_vjp(mlp['zs'][-1] if not relu else None, dA)
     else:
       g_raw_density, _ = ops.composite_bwd(
           lv['ccfg'], lv['raw_density'], lv['tdist'], R.directions, lv['weights'], density_noise=lv['dnoise'],
           bg=lv['bg'], g_rgb_out=g_rgb_out, g_weights=g_weights, want_f32=True, losses=losses, g_x_out=g_x_out)
       d = plan.density
-      if mlp.get('chain'):
+      if route.chain:
         # fused dX chain: head dW / db from the last activation, then every dY_i in one launch; dW_i = x_{i-1}^T dY_i below
         w_head = flat[d.kernel_off:d.kernel_off + W]
         ops.small_head_bwd(x_last, W, g_raw_density.view(M, 1), w_head.view(W, 1), M=M, K=W, Cn=1, dX=None,
                            relu_mask=False, dW=gslice(d.kernel_off, W), db=gslice(d.bias_off, 1))
-        D = len(plan.trunk)
         # (keyed by level: the proposal levels' backward passes may run side by side on streams of their own)
         # (the last dY = mask * (g (x) w_head) is not stored when its only reader, the last layer's weight-gradient GEMM, can
         # build it from the factors: `_rank1_last`)
-        r1 = _rank1_last(plan, D, W, g_feat_out is not None)
+        r1 = self._rank1_last(plan, g_feat_out is not None)
         dYs = [None if (r1 and i == D - 1) else self._buf(('bwd', slot, 'dYc', W, i, lv['level']), (M, W), bf16) for i in range(D)]
-        Bws = [None] + [self._w(plan, plan.packed[('trunk', i)]['b_off'], _rup(W, 128), plan.packed[('trunk', i)]['b_ld'])
-                        for i in range(1, D)]
-        ops.mlp_chain_bwd(g_raw_density.view(M), w_head, mlp['bits'], Bws, dYs, M=M, W=W)
+        ops.mlp_chain_bwd(g_raw_density.view(M), w_head, mlp['bits'], self._chain_bws(plan), dYs, M=M, W=W)
         feat = lv['feat']
-        for i, (dl, concat) in enumerate(plan.trunk):
-          inp, in_w, kv = (feat, plan.ldF, plan.F) if i == 0 else (acts[i - 1], W, W)
-          ops.gemm_tn(inp, dYs[i], gslice(dl.kernel_off, kv * W), M=M, K=in_w, N=W, lda=in_w, ldb=W, ldc=W,
-                      k_valid=kv, n_valid=W, bias_out=gslice(dl.bias_off, W), bias_n_valid=W,
-                      rank1=(g_raw_density.view(M), w_head, mlp['bits'][i]) if dYs[i] is None else None)
-          if concat:
-            ops.gemm_tn(feat, dYs[i], gslice(dl.kernel_off + W * W, plan.F * W), M=M, K=plan.ldF, N=W,
-                        lda=plan.ldF, ldb=W, ldc=W, k_valid=plan.F, n_valid=W)
+        for i, (_, concat) in enumerate(plan.trunk):
+          self._trunk_dw(plan, grads, i, acts, feat, dYs[i], M,
+                         rank1=(g_raw_density.view(M), w_head, mlp['bits'][i]) if dYs[i] is None else None)
           if i == 0 or concat:
             feat_grad(i, dYs[i])
         return
@@ -1836,20 +1867,13 @@ class Model:
     t_extras = None
     if g_raw_grad is not None:
       t_extras = self._tangent_backward(plan, flat, grads, mlp, feat, M, g_raw_grad, slot, g_tfeat_out)
-    if mlp.get('chain_trunk'):
+    if route.chain_trunk:
       # fused dX chain from the dY_last the head GEMMs left in dA; then dW_i = [x_{i-1} | feat]^T dY_i per layer
       dYs = [self._buf(('bwd', slot, 'dYc', W, i), (M, W), bf16) for i in range(D - 1)] + [None]
-      Bws = [None] + [self._w(plan, plan.packed[('trunk', i)]['b_off'], _rup(W, 128), plan.packed[('trunk', i)]['b_ld'])
-                      for i in range(1, D)]
-      ops.mlp_chain_bwd(None, None, mlp['bits'], Bws, dYs, M=M, W=W, dY_in=dA)
+      ops.mlp_chain_bwd(None, None, mlp['bits'], self._chain_bws(plan), dYs, M=M, W=W, dY_in=dA)
       dYs[D - 1] = dA
-      for i, (d, concat) in enumerate(plan.trunk):
-        inp, in_w, kv = (feat, plan.ldF, plan.F) if i == 0 else (acts[i - 1], W, W)
-        ops.gemm_tn(inp, dYs[i], gslice(d.kernel_off, kv * W), M=M, K=in_w, N=W, lda=in_w, ldb=W, ldc=W,
-                    k_valid=kv, n_valid=W, bias_out=gslice(d.bias_off, W), bias_n_valid=W)
-        if concat:
-          ops.gemm_tn(feat, dYs[i], gslice(d.kernel_off + W * W, plan.F * W), M=M, K=plan.ldF, N=W,
-                      lda=plan.ldF, ldb=W, ldc=W, k_valid=plan.F, n_valid=W)
+      for i, (_, concat) in enumerate(plan.trunk):
+        self._trunk_dw(plan, grads, i, acts, feat, dYs[i], M)
         if i == 0 or concat:
           feat_grad(i, dYs[i])
       return
@@ -1874,8 +1898,7 @@ class Model:
 
     try:
       for i in reversed(range(len(plan.trunk))):
-        d, concat = plan.trunk[i]
-        e = plan.packed[('trunk', i)]
+        concat = plan.trunk[i][1]
         if t_extras is not None:
           ops.add_cols_bf16(dy, t_extras[i], dy, W)        # the tangent network's act'' term of this layer's pre-activation
         if pair and i > 0:
@@ -1884,43 +1907,27 @@ class Model:
           ready.record(cur_s)
           self._dw_stream.wait_event(ready)
           with torch.cuda.stream(self._dw_stream):
-            ops.gemm_tn(acts[i - 1], dy, gslice(d.kernel_off, W * W), M=M, K=W, N=W, lda=W, ldb=W, ldc=W,
-                        bias_out=gslice(d.bias_off, W), bias_n_valid=W, m_interleave=True, max_wgs=self._half_cus, **tn_a, **tn_b)
-            if concat:
-              ops.gemm_tn(feat, dy, gslice(d.kernel_off + W * W, plan.F * W), M=M, K=plan.ldF, N=W,
-                          lda=plan.ldF, ldb=W, ldc=W, k_valid=plan.F, n_valid=W, **tn_b)
+            self._trunk_dw(plan, grads, i, acts, feat, dy, M, panel=panel, m_interleave=True, max_wgs=self._half_cus)
             done = pair_event('done', i)
             done.record(self._dw_stream)
           if concat:
             feat_grad(i, dy, dy_panel=panel)
           if dw_done is not None:
             cur_s.wait_event(dw_done)                      # dX_i overwrites the buffer dW_{i+1} read its dY from
-          Bw = self._w(plan, e['b_off'], _rup(W, 128), e['b_ld'])
           other = dy_buf(i - 1)
-          ops.gemm_nt(dy, Bw, M=M, N=_rup(W, 128), K1=e['b_ld'], Cb=other, ldcb=W, nb=W, max_wgs=self._half_cus,
-                      **mask_kw(i - 1), **lay_ac)
+          self._trunk_dx(plan, i, dy, other, M, max_wgs=self._half_cus, **mask_kw(i - 1), **lay_ac)
           dw_done = done
           dy = other
           continue
         if pair and dw_done is not None:
           cur_s.wait_event(dw_done)
           dw_done = None
-        if i == 0:
-          ops.gemm_tn(feat, dy, gslice(d.kernel_off, plan.F * W), M=M, K=plan.ldF, N=W, lda=plan.ldF, ldb=W,
-                      ldc=W, k_valid=plan.F, n_valid=W, bias_out=gslice(d.bias_off, W), bias_n_valid=W, **tn_b)
-        else:
-          ops.gemm_tn(acts[i - 1], dy, gslice(d.kernel_off, W * W), M=M, K=W, N=W, lda=W, ldb=W, ldc=W,
-                      bias_out=gslice(d.bias_off, W), bias_n_valid=W, **tn_a, **tn_b)
-          if concat:
-            ops.gemm_tn(feat, dy, gslice(d.kernel_off + W * W, plan.F * W), M=M, K=plan.ldF, N=W,
-                        lda=plan.ldF, ldb=W, ldc=W, k_valid=plan.F, n_valid=W, **tn_b)
+        self._trunk_dw(plan, grads, i, acts, feat, dy, M, panel=panel)
         if i == 0 or concat:
           feat_grad(i, dy, dy_panel=panel)
         if i > 0:
-          Bw = self._w(plan, e['b_off'], _rup(W, 128), e['b_ld'])
           other = dy_buf(i - 1)
-          ops.gemm_nt(dy, Bw, M=M, N=_rup(W, 128), K1=e['b_ld'], Cb=other, ldcb=W, nb=W, walk_descending=bool(i & 1),
-                      **mask_kw(i - 1), **lay_ac)
+          self._trunk_dx(plan, i, dy, other, M, walk_descending=bool(i & 1), **mask_kw(i - 1), **lay_ac)
           act_vjp(mlp['zs'][i - 1] if not relu else None, other)
           dy = other
     finally:
@@ -1942,7 +1949,7 @@ class Model:
     R = self._saved['rays']
     g_all = self._buf(('bwd', 'g_props', Lg), (Mall,), f32)
     for k, lv in enumerate(lvs):
-      assert lv['group'] == (k, Lg) and lv['M'] == M and lv['plan'] is plan and lv['mlp'].get('chain')
+      assert lv['group'] == (k, Lg) and lv['M'] == M and lv['plan'] is plan and lv['mlp']['route'].chain
       ops.composite_bwd(lv['ccfg'], lv['raw_density'], lv['tdist'], R.directions, lv['weights'],
                         density_noise=lv['dnoise'], bg=lv['bg'], g_rgb_out=None, g_weights=g_weights[k], want_f32=True,
                         losses=losses[k], g_raw_density_out=g_all[k * M:(k + 1) * M].view(lv['raw_density'].shape))
@@ -1957,20 +1964,11 @@ class Model:
     w_head = flat[d.kernel_off:d.kernel_off + W]
     ops.small_head_bwd(acts[-1], W, g_all.view(Mall, 1), w_head.view(W, 1), M=Mall, K=W, Cn=1, dX=None,
                        relu_mask=False, dW=grads[d.kernel_off:d.kernel_off + W], db=grads[d.bias_off:d.bias_off + 1])
-    r1 = _rank1_last(plan, D, W, False)
+    r1 = self._rank1_last(plan, False)
     dYs = [None if (r1 and i == D - 1) else self._buf(('bwd', 'dYc', W, i, 'props'), (Mall, W), bf16) for i in range(D)]
-    Bws = [None] + [self._w(plan, plan.packed[('trunk', i)]['b_off'], _rup(W, 128), plan.packed[('trunk', i)]['b_ld'])
-                    for i in range(1, D)]
-    ops.mlp_chain_bwd(g_all, w_head, bits, Bws, dYs, M=Mall, W=W)
-    for i, (dl, concat) in enumerate(plan.trunk):
-      inp, in_w, kv = (feat, plan.ldF, plan.F) if i == 0 else (acts[i - 1], W, W)
-      ops.gemm_tn(inp, dYs[i], grads[dl.kernel_off:dl.kernel_off + kv * W], M=Mall, K=in_w, N=W, lda=in_w, ldb=W,
-                  ldc=W, k_valid=kv, n_valid=W, bias_out=grads[dl.bias_off:dl.bias_off + W], bias_n_valid=W,
-                  rank1=(g_all, w_head, bits[i]) if dYs[i] is None else None)
-      if concat:
-        o = dl.kernel_off + W * W
-        ops.gemm_tn(feat, dYs[i], grads[o:o + plan.F * W], M=Mall, K=plan.ldF, N=W, lda=plan.ldF, ldb=W, ldc=W,
-                    k_valid=plan.F, n_valid=W)
+    ops.mlp_chain_bwd(g_all, w_head, bits, self._chain_bws(plan), dYs, M=Mall, W=W)
+    for i in range(D):
+      self._trunk_dw(plan, grads, i, acts, feat, dYs[i], Mall, rank1=(g_all, w_head, bits[i]) if dYs[i] is None else None)
 
   def _tangent_backward(self, plan, flat, grads, mlp, feat, M, g_raw_grad, slot, g_tfeat_out=None):
     """Backward pass through the tangent network T_l = bits_l * (T_{l-1} W_l), raw_grad = T_last w_density
@@ -1979,10 +1977,6 @@ class Model:
     W = plan.W
     M3 = 3 * M
     T_acts, T_feat, bits = mlp['T_acts'], mlp['T_feat'], mlp['bits']
-
-    def gslice(off, size):
-      return grads[off:off + size]
-
     gA = self._buf(('bwd', slot, 'gTA', W), (M3, W), bf16)
     gB = self._buf(('bwd', slot, 'gTB', W), (M3, W), bf16)
     d = plan.density
@@ -1992,22 +1986,20 @@ class Model:
     extras = None if relu else [self._buf(('bwd', slot, 'T_extra', W, i), (M, W), bf16) for i in range(len(plan.trunk))]
     # G_last = bits_last * (g_raw_grad[:, None] w_density^T);  dW_density += T_last^T g_raw_grad
     ops.small_head_bwd(T_acts[-1], W, g_raw_grad.view(M3, 1), flat[d.kernel_off:d.kernel_off + W].view(W, 1),
-                       M=M3, K=W, Cn=1, dX=gA, lddx=W, relu_mask=False, dW=gslice(d.kernel_off, W), db=None,
+                       M=M3, K=W, Cn=1, dX=gA, lddx=W, relu_mask=False, dW=grads[d.kernel_off:d.kernel_off + W], db=None,
                        bits=bits[-1] if relu else None, bits_row_mod=M if relu else 0)
     gy, other = gA, gB
     D = len(plan.trunk)
     Gs = None
-    if _TANGENT_CHAIN and relu and D >= 2 and self._chain_ok(plan) and all(b is not None for b in bits):
+    if _TANGENT_CHAIN and relu and D >= 2 and mlp['route'].fused and all(b is not None for b in bits):
       # every G_i in one masked-linear chain launch per direction (`_TANGENT_CHAIN`), kept for the weight-gradient GEMMs below
       Gs = [self._buf(('bwd', slot, 'gT', W, i), (M3, W), bf16) for i in range(D - 1)] + [gA]
-      Bws = [None] + [self._w(plan, plan.packed[('trunk', i)]['b_off'], _rup(W, 128), plan.packed[('trunk', i)]['b_ld'])
-                      for i in range(1, D)]
+      Bws = self._chain_bws(plan)
       for c in range(3):
         rows = slice(c * M, (c + 1) * M)
         ops.mlp_chain_bwd(None, None, bits, Bws, [g[rows] for g in Gs[:-1]] + [None], M=M, W=W, dY_in=gA[rows])
-    for i in reversed(range(len(plan.trunk))):
-      d, concat = plan.trunk[i]
-      e = plan.packed[('trunk', i)]
+    for i in reversed(range(D)):
+      concat, e = plan.trunk[i][1], plan.packed[('trunk', i)]
       if Gs is not None:
         gy = Gs[i]
       if not relu:
@@ -2019,19 +2011,10 @@ class Model:
         ops.gemm_nt(gy, self._w(plan, e['bf_off'], plan.ldF, e['bf_ld']), M=M3, N=plan.ldF, K1=e['bf_ld'], Cb=gT, ldcb=plan.ldF,
                     nb=plan.ldF)
         g_tfeat_out.append(gT)
-      if i == 0:
-        ops.gemm_tn(T_feat, gy, gslice(d.kernel_off, plan.F * W), M=M3, K=plan.ldF, N=W, lda=plan.ldF, ldb=W,
-                    ldc=W, k_valid=plan.F, n_valid=W)
-      else:
-        ops.gemm_tn(T_acts[i - 1], gy, gslice(d.kernel_off, W * W), M=M3, K=W, N=W, lda=W, ldb=W, ldc=W)
-        if concat:
-          ops.gemm_tn(T_feat, gy, gslice(d.kernel_off + W * W, plan.F * W), M=M3, K=plan.ldF, N=W,
-                      lda=plan.ldF, ldb=W, ldc=W, k_valid=plan.F, n_valid=W)
-        if Gs is None:
-          Bw = self._w(plan, e['b_off'], _rup(W, 128), e['b_ld'])
-          ops.gemm_nt(gy, Bw, M=M3, N=_rup(W, 128), K1=e['b_ld'], Cb=other, ldcb=W, nb=W,
-                      **(dict(bits_in=bits[i - 1], bits_row_mod=M) if relu else {}))
-          gy, other = other, gy
+      self._trunk_dw(plan, grads, i, T_acts, T_feat, gy, M3, bias=False)
+      if i > 0 and Gs is None:
+        self._trunk_dx(plan, i, gy, other, M3, **(dict(bits_in=bits[i - 1], bits_row_mod=M) if relu else {}))
+        gy, other = other, gy
     return extras
 
 
