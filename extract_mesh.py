@@ -1,0 +1,92 @@
+#!/usr/bin/env python
+"""Mesh extraction script: restore the latest checkpoint and write the isosurface of the NeRF level's density inside a box
+as a PLY file (binary_little_endian 1.0; positions, normals, optionally vertex colours, triangles).
+
+The density is queried on a regular grid on the device (`Model.query_density`, chunk by chunk), the surface is taken by
+marching tetrahedra on the device (`ops.marching_tetrahedra`, csrc/mesh.hip) and coloured by the NeRF MLP seen head-on
+(`multinerf_amd.mesh`).  --bbox is in world coordinates; the default is the linear region of the contraction, larger boxes
+are legal (the query warps like any other).  --density_threshold is scene-dependent: a decision, not a derived number.
+
+  python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
+      --resolution 512 --density_threshold 10 --out garden.ply
+"""
+
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+from multinerf_amd import checkpoints, configs, mesh, ops, train_utils
+
+
+def parse_args(argv):
+  """(args, box) of the command line `argv`; box = [x0, y0, z0, x1, y1, z1]."""
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--gin_configs', action='append', default=[])
+  ap.add_argument('--gin_bindings', action='append', default=[])
+  ap.add_argument('--preset', default=None)
+  ap.add_argument('--resolution', type=int, default=256, help='grid points along the longest side of the box')
+  ap.add_argument('--bbox', default='-1,-1,-1,1,1,1', help='x0,y0,z0,x1,y1,z1 in world coordinates')
+  ap.add_argument('--density_threshold', type=float, default=10.0, help='the isosurface level (scene-dependent)')
+  ap.add_argument('--std', type=float, default=0.5, help='standard deviation of the query Gaussians in grid spacings (0: point samples)')
+  ap.add_argument('--chunk', type=int, default=mesh.DEFAULT_CHUNK, help='points per MLP call')
+  ap.add_argument('--no_colors', action='store_true')
+  ap.add_argument('--out', default=None, help='default: <checkpoint_dir>/mesh/mesh_step_<step>.ply')
+  # `--bbox -1,-1,-1,1,1,1`: argparse takes a value that starts with '-' and is no plain number for an option; hand it over as --bbox=...
+  argv = list(argv)
+  for i in range(len(argv) - 1):
+    if argv[i] == '--bbox':
+      argv[i:i + 2] = ['--bbox=' + argv[i + 1]]
+      break
+  args = ap.parse_args(argv)
+  try:
+    box = [float(v) for v in args.bbox.split(',')]
+    if len(box) != 6:
+      raise ValueError
+  except ValueError:
+    raise SystemExit(f'extract_mesh.py: --bbox {args.bbox!r} must be six numbers x0,y0,z0,x1,y1,z1') from None
+  return args, box
+
+
+def main():
+  args, box = parse_args(sys.argv[1:])
+  dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
+  torch.cuda.set_device(dev)
+  config = configs.load_preset(args.preset, args.gin_bindings) if args.preset else \
+      configs.load_config(args.gin_configs, args.gin_bindings, save_config=False)
+  model, state, _, _, _ = train_utils.setup_model(config, 20200823, dataset=None, device=dev)
+  if not config.checkpoint_dir or checkpoints.latest_checkpoint(config.checkpoint_dir) is None:
+    raise SystemExit(f'extract_mesh.py: no checkpoint in Config.checkpoint_dir = {config.checkpoint_dir!r}')
+  state = checkpoints.restore_checkpoint(config.checkpoint_dir, model, state)
+  step = int(state.step)
+  print(f'Extracting a mesh from the checkpoint at step {step}.')
+  out = args.out or os.path.join(config.checkpoint_dir, 'mesh', f'mesh_step_{step}.ply')
+
+  def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.time()
+    r = fn()
+    torch.cuda.synchronize()
+    return r, time.time() - t0
+
+  (field, origin, spacing), t_grid = timed(lambda: mesh.density_grid(
+      lambda x, s: model.query_density(x[None], s)[0], box[:3], box[3:], args.resolution, std=args.std, chunk=args.chunk, device=dev))
+  print(f'grid {tuple(field.shape)}, spacing {spacing:.6g}, density min {float(field.min()):.4g} max {float(field.max()):.4g}')
+  (verts, normals, faces), t_iso = timed(lambda: ops.marching_tetrahedra(field, args.density_threshold, origin, spacing))
+  colors, t_col = None, 0.
+  if not args.no_colors:
+    colors, t_col = timed(lambda: mesh.vertex_colors(model, verts, normals, args.std * spacing, args.chunk))
+  result = dict(vertices=verts, normals=normals, faces=faces, colors=colors)
+  os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+  _, t_write = timed(lambda: mesh.write_ply(out, result))
+  stats = mesh.mesh_stats(verts, faces)
+  print('mesh_stats: ' + ', '.join(f'{k} {v:.6g}' if isinstance(v, float) else f'{k} {v}' for k, v in stats.items()))
+  print(f'seconds: grid query {t_grid:.3f} ({field.numel() / max(t_grid, 1e-9):.4g} points/s), isosurface {t_iso:.3f}, '
+        f'colour query {t_col:.3f}, file write {t_write:.3f}')
+  print(f'wrote {out}')
+
+
+if __name__ == '__main__':
+  main()

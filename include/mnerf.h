@@ -884,6 +884,47 @@ typedef enum { MNR_INGEST_PLAIN = 0, MNR_INGEST_WHITE_BG = 1, MNR_INGEST_NORMALS
 int mnr_image_ingest(int N, int H, int W, int C, int dtype, const void* src, int n_downsample, int mode, int C_out,
                      float* out, float* alpha, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Mesh extraction: marching tetrahedra on a regular grid  (csrc/mesh.hip)
+ * field [nx,ny,nz] float32, every dimension >= 2, field[i,j,k] at origin + spacing (i,j,k); linear point index
+ * p = (i ny + j) nz + k; a point is inside iff field >= level (a NaN is outside).  Every cell is cut into the 6 Kuhn
+ * tetrahedra, one per permutation (a, b, c) of the axes in lexicographic order (corners p, p + e_a, p + e_a + e_b,
+ * p + (1,1,1)); an edge leaves its lower end in one of the 7 directions (1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1),
+ * (0,1,1), (1,1,1) and carries a vertex iff its ends differ.  Vertices are ordered by lower-end index, then direction:
+ * the id of edge (p, e) is base[p] + popcount(mask[p] & ((1 << e) - 1)).  A vertex is P0 + t (P1 - P0) with
+ * t = (level - f0) / (f1 - f0) (0.5 where that is outside [0, 1] or NaN) and P = origin + spacing float(index), float32,
+ * no contraction; its normal is -g / |g| (0 where |g| is 0 or not finite) of the field gradient (central differences,
+ * one-sided at the grid faces, over the spacing) interpolated with the same t.  Faces are ordered by cell index, then
+ * tetrahedron, then triangle, counter-clockwise seen from the low-field side.  No atomics: two runs agree bit for bit.
+ *
+ * A workgroup owns 256 consecutive linear indices; mnr_mt_workgroups(n_points) is their number.  The caller runs
+ * mnr_mt_classify (mask, counts), takes the exclusive scan of counts over the workgroups as int64 (offsets) and the totals
+ * (n_verts, n_faces, both below 2^31), then mnr_mt_emit_vertices (base, verts, normals) and mnr_mt_emit_faces (faces).
+ * The emit passes tolerate a mask or offsets that are not this field's (a stale workspace): mask bits of edges that leave the
+ * grid are ignored, and nothing is written at or beyond row n_verts of verts / normals or row n_faces of faces; what is written
+ * is then meaningless, but no access leaves the grid or the outputs.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int nx, ny, nz;
+  const float* field;              /* [nx,ny,nz] */
+  float level;
+  float origin[3];
+  float spacing;                   /* > 0, finite */
+  unsigned char* mask;             /* [points]: written by classify, read by the emit passes */
+  int* counts;                     /* [workgroups,2]: (vertices, triangles) per workgroup, written by classify */
+  const int64_t* offsets;          /* [workgroups,2]: exclusive scan of counts (emit passes) */
+  int* base;                       /* [points]: written by emit_vertices, read by emit_faces */
+  float* verts;                    /* [n_verts,3] */
+  float* normals;                  /* [n_verts,3] */
+  int64_t n_verts;
+  int* faces;                      /* [n_faces,3] */
+  int64_t n_faces;
+} mnr_mt_args;
+int64_t mnr_mt_workgroups(int64_t n_points);
+int mnr_mt_classify(const mnr_mt_args* args, void* stream);
+int mnr_mt_emit_vertices(const mnr_mt_args* args, void* stream);
+int mnr_mt_emit_faces(const mnr_mt_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -203,6 +203,12 @@ IMG_DTYPE = {'uint8': 0, 'float32': 1}         # mnr_img_dtype
 INGEST_MODE = {'plain': 0, 'white_bg': 1, 'normals': 2}      # mnr_ingest_mode
 
 
+class MtArgs(C.Structure):
+  _fields_ = [('nx', C.c_int), ('ny', C.c_int), ('nz', C.c_int), ('field', vp), ('level', C.c_float), ('origin', C.c_float * 3),
+              ('spacing', C.c_float), ('mask', vp), ('counts', vp), ('offsets', vp), ('base', vp), ('verts', vp), ('normals', vp),
+              ('n_verts', C.c_int64), ('faces', vp), ('n_faces', C.c_int64)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
@@ -292,6 +298,10 @@ _PROTOS = {
     'mnr_affine_sums': ([i64, vp, vp, vp, vp, vp], i32),
     'mnr_affine_apply': ([i64, vp, C.POINTER(C.c_double), C.POINTER(C.c_double), vp, vp], i32),
     'mnr_image_ingest': ([i32, i32, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp], i32),
+    'mnr_mt_workgroups': ([i64], i64),
+    'mnr_mt_classify': ([C.POINTER(MtArgs), vp], i32),
+    'mnr_mt_emit_vertices': ([C.POINTER(MtArgs), vp], i32),
+    'mnr_mt_emit_faces': ([C.POINTER(MtArgs), vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

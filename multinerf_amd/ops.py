@@ -6,6 +6,7 @@ dtype and contiguity and then passes raw device pointers.
 """
 
 import ctypes as C
+import math
 import os
 
 import torch
@@ -1554,3 +1555,58 @@ def image_ingest(src, n_downsample=1, mode='plain', c_out=None, want_alpha=False
   if alpha is None:
     return out
   return out, alpha.reshape(shape[1:3] if single else shape[:3])
+
+
+# ----------------------------------------------------------------------------- mesh extraction (csrc/mesh.hip)
+
+
+def marching_tetrahedra(field, level, origin, spacing):
+  """Marching tetrahedra on a regular grid (mnr_mt_classify / mnr_mt_emit_vertices / mnr_mt_emit_faces): field [nx,ny,nz]
+  float32 with field[i,j,k] at origin + spacing (i,j,k), inside iff field >= level.  Returns the indexed mesh
+  (verts [V,3] float32, normals [V,3] float32, faces [T,3] int32) on the device: vertices ordered by the lower end's linear
+  index and edge direction, faces by cell, tetrahedron and triangle, counter-clockwise seen from the low-field side; normals
+  point toward lower field.  An isosurface that does not cross the grid gives V = T = 0.  The output sizes depend on the data:
+  the per-workgroup counts are scanned with torch.cumsum and the two totals are read back once (the call's one
+  synchronisation)."""
+  if not torch.is_tensor(field) or not _on_device(field):
+    raise ValueError('marching_tetrahedra: field must be a device tensor (the HIP path has no CPU fallback)')
+  if field.dtype != f32:
+    raise ValueError(f'marching_tetrahedra: field must be {f32}, is {field.dtype}')
+  if field.dim() != 3 or min(field.shape) < 2:
+    raise ValueError(f'marching_tetrahedra: field must be [nx,ny,nz] with every dimension >= 2, is {tuple(field.shape)}')
+  if not field.is_contiguous():
+    raise ValueError('marching_tetrahedra: field must be contiguous')
+  spacing = float(spacing)
+  if not (spacing > 0. and math.isfinite(spacing)):
+    raise ValueError(f'marching_tetrahedra: spacing must be positive and finite, is {spacing}')
+  origin = [float(v) for v in (origin.tolist() if torch.is_tensor(origin) else origin)]
+  if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+    raise ValueError(f'marching_tetrahedra: origin must hold 3 finite values, is {origin}')
+  dev = field.device
+  nx, ny, nz = (int(v) for v in field.shape)
+  n = nx * ny * nz
+  nwg = int(lib().mnr_mt_workgroups(n))
+  mask = torch.empty((n,), dtype=torch.uint8, device=dev)
+  counts = torch.empty((nwg, 2), dtype=torch.int32, device=dev)
+  a = L.MtArgs()
+  a.nx, a.ny, a.nz, a.field, a.level, a.spacing = nx, ny, nz, field.data_ptr(), float(level), spacing
+  a.origin[0], a.origin[1], a.origin[2] = origin
+  a.mask, a.counts = mask.data_ptr(), counts.data_ptr()
+  L.check(lib().mnr_mt_classify(C.byref(a), _stream()))
+  per = counts.t().contiguous()                             # [2, workgroups]: the scan runs along the contiguous dimension
+  ends = torch.cumsum(per, 1, dtype=torch.int64)
+  offsets = (ends - per).t().contiguous()
+  V, T = (int(v) for v in ends[:, -1].tolist())
+  if V >= 2 ** 31 or T >= 2 ** 31:
+    raise ValueError(f'marching_tetrahedra: {V} vertices and {T} triangles: both must stay below 2^31 (use a coarser grid)')
+  verts = torch.empty((V, 3), dtype=f32, device=dev)
+  normals = torch.empty((V, 3), dtype=f32, device=dev)
+  faces = torch.empty((T, 3), dtype=torch.int32, device=dev)
+  if V == 0:
+    return verts, normals, faces
+  base = torch.empty((n,), dtype=torch.int32, device=dev)
+  a.offsets, a.base = offsets.data_ptr(), base.data_ptr()
+  a.verts, a.normals, a.n_verts, a.faces, a.n_faces = verts.data_ptr(), normals.data_ptr(), V, faces.data_ptr(), T
+  L.check(lib().mnr_mt_emit_vertices(C.byref(a), _stream()))
+  L.check(lib().mnr_mt_emit_faces(C.byref(a), _stream()))
+  return verts, normals, faces
