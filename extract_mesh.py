@@ -7,8 +7,16 @@ marching tetrahedra on the device (`ops.marching_tetrahedra`, csrc/mesh.hip) and
 (`multinerf_amd.mesh`).  --bbox is in world coordinates; the default is the linear region of the contraction, larger boxes
 are legal (the query warps like any other).  --density_threshold is scene-dependent: a decision, not a derived number.
 
+--method tsdf meshes what the model RENDERS instead: every --tsdf_stride-th camera of the --tsdf_split split is rendered as
+render.py renders it, and the depth (--tsdf_depth), opacity and colour images are fused into a truncated signed distance
+volume over the box (`mesh.tsdf_mesh`, csrc/tsdf.hip), whose zero set between observed voxels is the surface.  It has no level
+to choose; rays with opacity below --acc_threshold carve free space; colours come from the renders.  --tsdf_trunc, the
+truncation in grid spacings, is a decision: larger closes thin gaps and thickens thin structures.  Perspective cameras only.
+
   python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
       --resolution 512 --density_threshold 10 --out garden.ply
+  python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
+      --gin_bindings "Config.data_dir = '...'" --method tsdf --resolution 512 --out garden_tsdf.ply
 """
 
 import argparse
@@ -34,6 +42,14 @@ def parse_args(argv):
   ap.add_argument('--chunk', type=int, default=mesh.DEFAULT_CHUNK, help='points per MLP call')
   ap.add_argument('--no_colors', action='store_true')
   ap.add_argument('--out', default=None, help='default: <checkpoint_dir>/mesh/mesh_step_<step>.ply')
+  ap.add_argument('--method', choices=('density', 'tsdf'), default='density',
+                  help='density: the isosurface of the density; tsdf: fuse rendered depth into a truncated signed distance volume')
+  ap.add_argument('--tsdf_trunc', type=float, default=3.0,
+                  help='truncation distance in grid spacings (a decision: larger closes thin gaps and thickens thin structures)')
+  ap.add_argument('--tsdf_split', choices=('train', 'test'), default='train', help='the cameras to render')
+  ap.add_argument('--tsdf_stride', type=int, default=1, help='render every n-th camera')
+  ap.add_argument('--tsdf_depth', choices=('distance_median', 'distance_mean'), default='distance_median')
+  ap.add_argument('--acc_threshold', type=float, default=0.5, help='rays with less opacity are empty: they carve free space')
   # `--bbox -1,-1,-1,1,1,1`: argparse takes a value that starts with '-' and is no plain number for an option; hand it over as --bbox=...
   argv = list(argv)
   for i in range(len(argv) - 1):
@@ -71,6 +87,9 @@ def main():
     torch.cuda.synchronize()
     return r, time.time() - t0
 
+  if args.method == 'tsdf':
+    return main_tsdf(args, box, config, model, state, out, timed)
+
   (field, origin, spacing), t_grid = timed(lambda: mesh.density_grid(
       lambda x, s: model.query_density(x[None], s)[0], box[:3], box[3:], args.resolution, std=args.std, chunk=args.chunk, device=dev))
   print(f'grid {tuple(field.shape)}, spacing {spacing:.6g}, density min {float(field.min()):.4g} max {float(field.max()):.4g}')
@@ -85,6 +104,29 @@ def main():
   print('mesh_stats: ' + ', '.join(f'{k} {v:.6g}' if isinstance(v, float) else f'{k} {v}' for k, v in stats.items()))
   print(f'seconds: grid query {t_grid:.3f} ({field.numel() / max(t_grid, 1e-9):.4g} points/s), isosurface {t_iso:.3f}, '
         f'colour query {t_col:.3f}, file write {t_write:.3f}')
+  print(f'wrote {out}')
+
+
+def main_tsdf(args, box, config, model, state, out, timed):
+  from multinerf_amd import datasets
+  dataset = datasets.load_dataset(args.tsdf_split, config.data_dir, config, device=model.device)
+  seconds = {}
+  result, volume = mesh.tsdf_mesh(model, state.params, dataset, config, box[:3], box[3:], args.resolution, trunc_voxels=args.tsdf_trunc,
+                                  depth_key=args.tsdf_depth, acc_threshold=args.acc_threshold, frame_stride=args.tsdf_stride,
+                                  colors=not args.no_colors, timings=seconds)
+  frames = len(range(0, dataset.size, args.tsdf_stride))
+  print(f'grid {tuple(volume.shape)}, spacing {volume.spacing:.6g}, truncation {volume.trunc:.6g}, {frames} frames of '
+        f'{dataset.height} x {dataset.width} ({args.tsdf_split} split, {args.tsdf_depth})')
+  os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+  _, t_write = timed(lambda: mesh.write_ply(out, result))
+  stats = mesh.mesh_stats(result['vertices'], result['faces'])
+  print('mesh_stats: ' + ', '.join(f'{k} {v:.6g}' if isinstance(v, float) else f'{k} {v}' for k, v in stats.items()))
+  unseen, total = int((volume.weight == 0).sum()), volume.weight.numel()
+  print(f'never observed: {unseen} of {total} voxels ({unseen / total:.2%})')
+  before = int(ops.marching_tetrahedra(volume.field()[0], 0., volume.origin, volume.spacing)[2].shape[0])
+  print(f'faces: {before} before the validity filter, {stats["T"]} after')
+  print(f'seconds: render {seconds["render"]:.3f}, fusion {seconds["fusion"]:.3f}, isosurface {seconds["isosurface"]:.3f}, '
+        f'file write {t_write:.3f}')
   print(f'wrote {out}')
 
 

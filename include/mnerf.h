@@ -925,6 +925,48 @@ int mnr_mt_classify(const mnr_mt_args* args, void* stream);
 int mnr_mt_emit_vertices(const mnr_mt_args* args, void* stream);
 int mnr_mt_emit_faces(const mnr_mt_args* args, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * TSDF fusion of depth images into a regular grid, and vertex validity  (csrc/tsdf.hip)
+ * The grid is the one above: voxel (i,j,k) at origin + spacing (i,j,k), linear index p = (i ny + j) nz + k.  proj [F,3,4] maps
+ * world coordinates to (u zc, v zc, zc), pixel px covering [px, px + 1) and depth [F,H,W] holding zc of the surface (0, a
+ * negative value, an infinity or a NaN: no measurement).  Per voxel, frames f = 0 .. F - 1 in ascending order, float32 in the
+ * order written, no contraction:
+ *   1. x = origin[0] + spacing float(i), likewise y, z;
+ *   2. m_r = ((P[r][0] x + P[r][1] y) + P[r][2] z) + P[r][3] for r = 0, 1, 2; zc = m_2; skip the frame unless zc > 0;
+ *   3. u = m_0 / zc, v = m_1 / zc; skip unless 0 <= u < float(W) and 0 <= v < float(H); px = int(u), py = int(v);
+ *   4. if acc is given and acc[f,py,px] < acc_threshold the ray is empty: t = 1;
+ *   5. otherwise d = depth[f,py,px]; skip unless 0 < d < inf; s = d - zc; skip if s < -trunc; t = min(1, s / trunc);
+ *   6. sum_t += t, sum_w += 1, sum_c[c] += rgb[f,py,px,c];
+ *   7. after the last frame, if sum_w > 0: W0 = weight[p], Wn = W0 + sum_w, tsdf[p] = (W0 tsdf[p] + sum_t) / Wn,
+ *      color[p,c] = (W0 color[p,c] + sum_c[c]) / Wn, weight[p] = Wn; otherwise the voxel is not written.
+ * A launch stages at most MNR_TSDF_MAX_FRAMES matrices; a longer stack is integrated MNR_TSDF_MAX_FRAMES frames a launch, in
+ * order, each launch applying step 7 to its own sums (so F = 100 equals a call with the first 64 frames followed by a call
+ * with the other 36).  Within a launch every volume is read and written once.  F == 0 is a successful no-op.  No atomics: two
+ * runs agree bit for bit.
+ * ------------------------------------------------------------------------- */
+#define MNR_TSDF_MAX_FRAMES 64
+typedef struct {
+  int nx, ny, nz;
+  float origin[3];
+  float spacing;                   /* > 0, finite */
+  float trunc;                     /* world units, > 0, finite */
+  int F, H, W;
+  const float* proj;               /* [F,3,4] */
+  const float* depth;              /* [F,H,W] */
+  const float* acc;                /* [F,H,W] or NULL */
+  float acc_threshold;
+  const float* rgb;                /* [F,H,W,3] or NULL */
+  float* tsdf;                     /* [nx,ny,nz], updated in place */
+  float* weight;                   /* [nx,ny,nz], updated in place */
+  float* color;                    /* [nx,ny,nz,3] or NULL (rgb and color: both or neither), updated in place */
+} mnr_tsdf_args;
+int mnr_tsdf_integrate(const mnr_tsdf_args* args, void* stream);
+
+/* keep[id] = 1 iff both ends of vertex id's grid edge have valid != 0, else 0, for the vertices of a mesh the three passes above
+ * produced: args carries that run's nx, ny, nz, mask, base and n_verts; valid [points] and keep [n_verts] are bytes.  As in the
+ * emit passes, mask bits of edges that leave the grid are ignored and nothing is written at or beyond keep[n_verts]. */
+int mnr_mt_vertex_valid(const mnr_mt_args* args, const unsigned char* valid, unsigned char* keep, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

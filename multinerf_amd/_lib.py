@@ -209,6 +209,15 @@ class MtArgs(C.Structure):
               ('n_verts', C.c_int64), ('faces', vp), ('n_faces', C.c_int64)]
 
 
+TSDF_MAX_FRAMES = 64               # MNR_TSDF_MAX_FRAMES
+
+
+class TsdfArgs(C.Structure):
+  _fields_ = [('nx', C.c_int), ('ny', C.c_int), ('nz', C.c_int), ('origin', C.c_float * 3), ('spacing', C.c_float), ('trunc', C.c_float),
+              ('F', C.c_int), ('H', C.c_int), ('W', C.c_int), ('proj', vp), ('depth', vp), ('acc', vp), ('acc_threshold', C.c_float),
+              ('rgb', vp), ('tsdf', vp), ('weight', vp), ('color', vp)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
@@ -302,6 +311,8 @@ _PROTOS = {
     'mnr_mt_classify': ([C.POINTER(MtArgs), vp], i32),
     'mnr_mt_emit_vertices': ([C.POINTER(MtArgs), vp], i32),
     'mnr_mt_emit_faces': ([C.POINTER(MtArgs), vp], i32),
+    'mnr_tsdf_integrate': ([C.POINTER(TsdfArgs), vp], i32),
+    'mnr_mt_vertex_valid': ([C.POINTER(MtArgs), vp, vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

@@ -2,6 +2,9 @@
 
   density_grid   the field of a density function on a box, queried chunk by chunk on the device
   extract_mesh   density_grid of `model.query_density`, ops.marching_tetrahedra (csrc/mesh.hip), colours from `model.nerf_hp`
+  world_to_pixel the [3,4] projection of a perspective camera that csrc/tsdf.hip reads
+  TsdfVolume     a truncated signed distance volume: integrate depth images (ops.tsdf_integrate, csrc/tsdf.hip), mesh its zero set
+  tsdf_mesh      render the cameras of a dataset and fuse their depth into a TsdfVolume
   write_ply / read_ply   binary_little_endian 1.0
   mesh_stats     counts, Euler characteristic, open and non-manifold edges, signed volume, area (host, float64)
 
@@ -10,11 +13,12 @@ Grid convention (the kernels' own): field[i, j, k] sits at origin + spacing * (i
 """
 
 import math
+import time
 
 import numpy as np
 import torch
 
-from multinerf_amd import models, ops
+from multinerf_amd import camera_utils, models, ops
 
 # samples of one `mlp_call`: it keeps features, tangent rows and every layer's activations.  Measured for the 360 preset at
 # full width (1024-wide NeRF MLP), profiles/mesh_extract.md: 3.0 GiB peak allocation at 2^18 samples, i.e. about 12 KiB a sample
@@ -111,6 +115,157 @@ def extract_mesh(model, bbox_min, bbox_max, resolution, density_threshold, std=0
   if colors:
     cols = vertex_colors(model, verts, normals, float(std) * spacing, chunk)
   return dict(vertices=verts, normals=normals, faces=faces, colors=cols)
+
+
+def world_to_pixel(pixtocam, camtoworld, distortion_params=None, pixtocam_ndc=None, camtype=camera_utils.ProjectionType.PERSPECTIVE):
+  """The [3,4] float32 matrix P (a host array) with P @ (X, 1) = (u zc, v zc, zc) for a world point X seen by a perspective
+  camera: inv(pixtocam) @ diag(1, -1, -1) @ [R^T | -R^T o] with camtoworld = [R | o], computed in float64.  Pixel px covers
+  u in [px, px + 1), its centre is px + 0.5.
+
+  zc is the rendered distance.  camera_utils.pixels_to_rays (the reference's internal/camera_utils.py:560-610) builds the ray
+  of pixel (px, py) as directions = R diag(1, -1, -1) pixtocam (px + .5, py + .5, 1): for a perspective camera the last row of
+  pixtocam is (0, 0, 1), so the camera-space z of `directions` is -1 (it is NOT normalised), and the distance_mean /
+  distance_median a model renders along `directions` are exactly the zc of this matrix at the surface point: depth images
+  and projection agree without a conversion.
+
+  That holds for the undistorted pinhole model only, so everything else is refused with a ValueError: lens distortion
+  parameters, an NDC ray space (pixtocam_ndc), ProjectionType.FISHEYE, and the spherical 'pano' camera of render paths."""
+  if distortion_params is not None:
+    raise ValueError('world_to_pixel: distortion parameters are given: a distorted camera has no [3,4] projection matrix')
+  if pixtocam_ndc is not None:
+    raise ValueError('world_to_pixel: pixtocam_ndc is given: rays in NDC space are not the straight lines of a [3,4] projection')
+  if isinstance(camtype, str) and camtype == 'pano':
+    raise ValueError("world_to_pixel: the 'pano' camera is spherical: it has no [3,4] projection matrix")
+  if camera_utils.ProjectionType(camtype) == camera_utils.ProjectionType.FISHEYE:
+    raise ValueError('world_to_pixel: ProjectionType.FISHEYE: a fisheye camera has no [3,4] projection matrix')
+  K = np.linalg.inv(_host(pixtocam, np.float64).reshape(3, 3))
+  c2w = _host(camtoworld, np.float64)[..., :3, :4].reshape(3, 4)
+  R, o = c2w[:, :3], c2w[:, 3]
+  w2c = np.concatenate([R.T, -(R.T @ o)[:, None]], 1)
+  return np.ascontiguousarray(K @ np.diag([1., -1., -1.]) @ w2c, dtype=np.float32)
+
+
+# the 7 edge directions of csrc/mesh.hip, by edge number
+_EDGE_DIRS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
+
+
+class TsdfVolume:
+  """A truncated signed distance volume on the grid of `grid_shape` over a box (Curless-Levoy running averages): `tsdf`
+  [nx,ny,nz] in [-1, 1] in units of the truncation distance (starts at 1), `weight` [nx,ny,nz] the number of observations
+  (starts at 0), `color` [nx,ny,nz,3] (starts at 0; None with colors=False), all float32 on the device.  The truncation is
+  `trunc_voxels` grid spacings: a decision, not a derived number (larger closes thin gaps and thickens thin structures; below
+  about 2 the zero crossing is no longer bracketed on diagonal edges)."""
+
+  def __init__(self, bbox_min, bbox_max, resolution, trunc_voxels=3.0, colors=True, device='cuda'):
+    self.shape, self.spacing = grid_shape(bbox_min, bbox_max, resolution)
+    self.origin = tuple(float(np.float32(v)) for v in bbox_min)
+    self.trunc = float(np.float32(float(trunc_voxels) * self.spacing))
+    if not (self.trunc > 0. and math.isfinite(self.trunc)):
+      raise ValueError(f'trunc_voxels = {trunc_voxels} must be positive and finite')
+    self.tsdf = torch.ones(self.shape, dtype=torch.float32, device=device)
+    self.weight = torch.zeros(self.shape, dtype=torch.float32, device=device)
+    self.color = torch.zeros(self.shape + (3,), dtype=torch.float32, device=device) if colors else None
+
+  def integrate(self, depth, proj, acc=None, rgb=None, acc_threshold=0.5):
+    """Fuse one frame (depth [H,W], proj [3,4]) or a stack ([F,H,W], [F,3,4]): depth is zc along the rays of `world_to_pixel`'s
+    camera (0, negative, infinite or NaN: no measurement), acc (optional) the rays' opacity, below `acc_threshold` an empty ray
+    that marks what it crosses as free space, rgb [...,3] the colours (required with a colour volume, ignored without)."""
+    dev = self.tsdf.device
+    to = lambda x: None if x is None else torch.as_tensor(x).to(device=dev, dtype=torch.float32)
+    depth, proj, acc, rgb = to(depth), to(proj), to(acc), to(rgb)
+    if depth.dim() == 2:
+      depth, proj = depth[None], proj[None]
+      acc, rgb = (None if acc is None else acc[None]), (None if rgb is None else rgb[None])
+    if self.color is None:
+      rgb = None
+    elif rgb is None:
+      raise ValueError('TsdfVolume.integrate: a volume with colours needs rgb')
+    c = lambda x: None if x is None else x.contiguous()
+    ops.tsdf_integrate(self.tsdf, self.weight, self.color, self.origin, self.spacing, self.trunc, c(proj), c(depth), acc=c(acc),
+                       rgb=c(rgb), acc_threshold=acc_threshold)
+
+  def field(self):
+    """(field, valid): the field marching tetrahedra runs on, -tsdf where a voxel was observed and -1 elsewhere (inside, field >=
+    0, is BEHIND the surface), and the mask of observed voxels."""
+    valid = self.weight > 0
+    return torch.where(valid, -self.tsdf, torch.full_like(self.tsdf, -1.)), valid
+
+  def mesh(self):
+    """The zero set of the fused distance between observed voxels, as the dict `extract_mesh` returns.  Normals point into free
+    space and faces are counter-clockwise seen from there.  A vertex' colour is the colour volume interpolated along its grid
+    edge with the edge's t = (0 - f0) / (f1 - f0) in float32, then floor(clip(c, 0, 1) * 255 + 0.5)."""
+    field, valid = self.field()
+    verts, normals, faces, edges = ops.marching_tetrahedra(field, 0., self.origin, self.spacing, valid=valid, return_edges=True)
+    cols = None
+    if self.color is not None:
+      _, ny, nz = self.shape
+      step = torch.tensor([dx * ny * nz + dy * nz + dz for dx, dy, dz in _EDGE_DIRS], dtype=torch.int64, device=field.device)
+      p0 = edges[:, 0]
+      p1 = p0 + step[edges[:, 1]]
+      f, c = field.reshape(-1), self.color.reshape(-1, 3)
+      f0, f1 = f[p0], f[p1]
+      t = (0. - f0) / (f1 - f0)
+      t = torch.where((t >= 0.) & (t <= 1.), t, torch.full_like(t, 0.5))[:, None]
+      c0, c1 = c[p0], c[p1]
+      d = t * (c1 - c0)
+      cols = torch.floor(torch.clamp(c0 + d, 0., 1.) * 255. + 0.5).to(torch.uint8)
+    return dict(vertices=verts, normals=normals, faces=faces, colors=cols)
+
+
+def tsdf_mesh(model, params, dataset, config, bbox_min, bbox_max, resolution, trunc_voxels=3.0, depth_key='distance_median',
+              acc_threshold=0.5, frame_stride=1, frames_per_call=8, colors=True, timings=None):
+  """Render every `frame_stride`-th camera of `dataset` and fuse the rendered depth into a TsdfVolume over the box; returns
+  (the mesh dict of TsdfVolume.mesh, the volume).
+
+  The frames are rendered the way render.py renders them (train_utils.create_render_fn, models.render_image, rng=None) with
+  the bound parameters `params` (the `variables` of construct_model / a restored state's params); `depth_key`
+  ('distance_median' or 'distance_mean'), 'acc' and 'rgb' of `frames_per_call` frames are stacked and integrated in one call.
+  The cameras must be undistorted perspective cameras (`world_to_pixel` refuses the others).  A dict passed as `timings` gets the
+  seconds of 'render', 'fusion' and 'isosurface' (each bracketed by a device synchronisation)."""
+  from multinerf_amd import train_utils
+  if depth_key not in ('distance_median', 'distance_mean'):
+    raise ValueError(f"tsdf_mesh: depth_key = {depth_key!r} must be 'distance_median' or 'distance_mean'")
+  frame_stride, frames_per_call = int(frame_stride), int(frames_per_call)
+  if frame_stride < 1 or frames_per_call < 1:
+    raise ValueError('tsdf_mesh: frame_stride and frames_per_call must be positive')
+  camtype = 'pano' if getattr(dataset, '_render_spherical', False) else dataset.camtype
+  pixtocams = _host(dataset.pixtocams, np.float64)
+  volume = TsdfVolume(bbox_min, bbox_max, resolution, trunc_voxels=trunc_voxels, colors=colors, device=model.device)
+  render_fn = train_utils.create_render_fn(model)
+  seconds = dict(render=0., fusion=0., isosurface=0.)
+
+  def timed(key, fn):
+    if timings is None:
+      return fn()
+    torch.cuda.synchronize()
+    t0 = time.time()
+    r = fn()
+    torch.cuda.synchronize()
+    seconds[key] += time.time() - t0
+    return r
+
+  def flush(stack):
+    if stack:
+      depth, proj, acc, rgb = (torch.stack([s[n] for s in stack], 0) for n in range(4))
+      timed('fusion', lambda: volume.integrate(depth, proj, acc=acc, rgb=rgb if colors else None, acc_threshold=acc_threshold))
+    del stack[:]
+
+  stack = []
+  for idx in range(0, dataset.size, frame_stride):
+    proj = world_to_pixel(pixtocams if pixtocams.ndim == 2 else pixtocams[idx], dataset.camtoworlds[idx],
+                          distortion_params=dataset.distortion_params, pixtocam_ndc=dataset.pixtocam_ndc, camtype=camtype)
+    rays = dataset.generate_ray_batch(idx).rays
+    r = timed('render', lambda: models.render_image(lambda rng, chunk: render_fn(params, 1.0, None, chunk), rays, None, config,
+                                                    verbose=False))
+    stack.append((r[depth_key].to(torch.float32), torch.as_tensor(proj).to(model.device), r['acc'].to(torch.float32),
+                  r['rgb'].to(torch.float32)))
+    if len(stack) == frames_per_call:
+      flush(stack)
+  flush(stack)
+  result = timed('isosurface', volume.mesh)
+  if timings is not None:
+    timings.update(seconds)
+  return result, volume
 
 
 def _host(x, dtype):

@@ -1560,14 +1560,21 @@ def image_ingest(src, n_downsample=1, mode='plain', c_out=None, want_alpha=False
 # ----------------------------------------------------------------------------- mesh extraction (csrc/mesh.hip)
 
 
-def marching_tetrahedra(field, level, origin, spacing):
+def marching_tetrahedra(field, level, origin, spacing, valid=None, return_edges=False):
   """Marching tetrahedra on a regular grid (mnr_mt_classify / mnr_mt_emit_vertices / mnr_mt_emit_faces): field [nx,ny,nz]
   float32 with field[i,j,k] at origin + spacing (i,j,k), inside iff field >= level.  Returns the indexed mesh
   (verts [V,3] float32, normals [V,3] float32, faces [T,3] int32) on the device: vertices ordered by the lower end's linear
   index and edge direction, faces by cell, tetrahedron and triangle, counter-clockwise seen from the low-field side; normals
   point toward lower field.  An isosurface that does not cross the grid gives V = T = 0.  The output sizes depend on the data:
   the per-workgroup counts are scanned with torch.cumsum and the two totals are read back once (the call's one
-  synchronisation)."""
+  synchronisation).
+
+  valid ([nx,ny,nz] bool or uint8 on the device; None: the call, its launches and its results are as above) restricts the mesh
+  to observed points: a vertex is kept iff both ends of its grid edge are valid (mnr_mt_vertex_valid, csrc/tsdf.hip), a face
+  iff its three vertices are kept, vertices no kept face refers to are removed, and the faces are re-indexed; the order of the
+  surviving vertices and faces is unchanged.  (The compaction indexes with boolean masks: one more synchronisation each.)
+  return_edges=True appends edges [V,2] int64 to the result: per vertex the linear index of its edge's lower end and the
+  edge's direction number 0..6 ((1,0,0), (0,1,0), (0,0,1), (1,1,0), (1,0,1), (0,1,1), (1,1,1))."""
   if not torch.is_tensor(field) or not _on_device(field):
     raise ValueError('marching_tetrahedra: field must be a device tensor (the HIP path has no CPU fallback)')
   if field.dtype != f32:
@@ -1585,6 +1592,12 @@ def marching_tetrahedra(field, level, origin, spacing):
   dev = field.device
   nx, ny, nz = (int(v) for v in field.shape)
   n = nx * ny * nz
+  if valid is not None:
+    if not torch.is_tensor(valid) or not _on_device(valid) or valid.dtype not in (torch.bool, torch.uint8):
+      raise ValueError('marching_tetrahedra: valid must be a bool or uint8 device tensor')
+    if tuple(valid.shape) != (nx, ny, nz):
+      raise ValueError(f'marching_tetrahedra: valid {tuple(valid.shape)} must have the field\'s shape {(nx, ny, nz)}')
+    valid = valid.contiguous().view(torch.uint8)
   nwg = int(lib().mnr_mt_workgroups(n))
   mask = torch.empty((n,), dtype=torch.uint8, device=dev)
   counts = torch.empty((nwg, 2), dtype=torch.int32, device=dev)
@@ -1603,10 +1616,67 @@ def marching_tetrahedra(field, level, origin, spacing):
   normals = torch.empty((V, 3), dtype=f32, device=dev)
   faces = torch.empty((T, 3), dtype=torch.int32, device=dev)
   if V == 0:
-    return verts, normals, faces
+    return (verts, normals, faces) + ((torch.empty((0, 2), dtype=torch.int64, device=dev),) if return_edges else ())
   base = torch.empty((n,), dtype=torch.int32, device=dev)
   a.offsets, a.base = offsets.data_ptr(), base.data_ptr()
   a.verts, a.normals, a.n_verts, a.faces, a.n_faces = verts.data_ptr(), normals.data_ptr(), V, faces.data_ptr(), T
   L.check(lib().mnr_mt_emit_vertices(C.byref(a), _stream()))
   L.check(lib().mnr_mt_emit_faces(C.byref(a), _stream()))
-  return verts, normals, faces
+  edges = None
+  if return_edges:                                          # vertex order = (lower end, direction) order of the set mask bits
+    lower = torch.nonzero(mask).reshape(-1)
+    bits = (mask[lower, None] >> torch.arange(7, dtype=torch.uint8, device=dev)) & 1
+    at = torch.nonzero(bits)
+    edges = torch.stack([lower[at[:, 0]], at[:, 1]], -1)
+  if valid is not None:
+    keep = torch.empty((V,), dtype=torch.uint8, device=dev)
+    L.check(lib().mnr_mt_vertex_valid(C.byref(a), _ptr(valid), _ptr(keep), _stream()))
+    keep = keep != 0
+    faces = faces[keep[faces.long()].all(-1)]
+    used = torch.zeros((V,), dtype=torch.bool, device=dev)
+    used[faces.reshape(-1).long()] = True
+    new_id = (torch.cumsum(used, 0, dtype=torch.int64) - 1).to(torch.int32)
+    faces = new_id[faces.long()].reshape(-1, 3).contiguous()
+    verts, normals = verts[used].contiguous(), normals[used].contiguous()
+    if edges is not None:
+      edges = edges[used].contiguous()
+  return (verts, normals, faces) + ((edges,) if return_edges else ())
+
+
+# ----------------------------------------------------------------------------- TSDF fusion (csrc/tsdf.hip)
+
+
+def tsdf_integrate(tsdf, weight, color, origin, spacing, trunc, proj, depth, acc=None, rgb=None, acc_threshold=0.5):
+  """Fuse F depth images into the running TSDF average of a regular grid, in place (mnr_tsdf_integrate; include/mnerf.h states
+  the per-voxel steps): tsdf, weight [nx,ny,nz] float32 and color [nx,ny,nz,3] float32 or None, voxel (i,j,k) at
+  origin + spacing (i,j,k); proj [F,3,4] float32 (mesh.world_to_pixel), depth [F,H,W] float32, acc [F,H,W] float32 or None
+  (below acc_threshold: an empty ray, the voxel is free space), rgb [F,H,W,3] float32, given iff color is; trunc in world
+  units.  A stack longer than _lib.TSDF_MAX_FRAMES is integrated that many frames a launch.  Returns None."""
+  name = 'tsdf_integrate'
+  for t, label in ((tsdf, 'tsdf'), (weight, 'weight'), (proj, 'proj'), (depth, 'depth')):
+    _chk(t, f32, label)
+  _chk(color, f32, 'color', allow_none=True)
+  _chk(acc, f32, 'acc', allow_none=True)
+  _chk(rgb, f32, 'rgb', allow_none=True)
+  if tsdf.dim() != 3 or weight.shape != tsdf.shape or (color is not None and tuple(color.shape) != tuple(tsdf.shape) + (3,)):
+    raise ValueError(f'{name}: tsdf and weight must be [nx,ny,nz] and color [nx,ny,nz,3]')
+  if (color is None) != (rgb is None):
+    raise ValueError(f'{name}: rgb and color are both given or both None')
+  if depth.dim() != 3 or proj.dim() != 3 or tuple(proj.shape) != (depth.shape[0], 3, 4):
+    raise ValueError(f'{name}: depth must be [F,H,W] and proj [F,3,4], are {tuple(depth.shape)} and {tuple(proj.shape)}')
+  if (acc is not None and acc.shape != depth.shape) or (rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,)):
+    raise ValueError(f'{name}: acc must be [F,H,W] and rgb [F,H,W,3] for depth {tuple(depth.shape)}')
+  spacing, trunc = float(spacing), float(trunc)
+  if not (spacing > 0. and math.isfinite(spacing)) or not (trunc > 0. and math.isfinite(trunc)):
+    raise ValueError(f'{name}: spacing and trunc must be positive and finite, are {spacing} and {trunc}')
+  origin = [float(v) for v in (origin.tolist() if torch.is_tensor(origin) else origin)]
+  if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+    raise ValueError(f'{name}: origin must hold 3 finite values, is {origin}')
+  a = L.TsdfArgs()
+  a.nx, a.ny, a.nz = (int(v) for v in tsdf.shape)
+  a.origin[0], a.origin[1], a.origin[2] = origin
+  a.spacing, a.trunc, a.acc_threshold = spacing, trunc, float(acc_threshold)
+  a.F, a.H, a.W = (int(v) for v in depth.shape)
+  a.proj, a.depth, a.acc, a.rgb = proj.data_ptr(), depth.data_ptr(), _ptr(acc), _ptr(rgb)
+  a.tsdf, a.weight, a.color = tsdf.data_ptr(), weight.data_ptr(), _ptr(color)
+  L.check(lib().mnr_tsdf_integrate(C.byref(a), _stream()))
