@@ -14,8 +14,9 @@
 //
 // Work split inside a 256-thread block handling SPB consecutive samples:
 //   phase 1: one thread per sample: Gaussian (mean, cov), warp -> LDS
-//   phase 2: one thread per (sample, basis direction): projection, then the L degrees
-//   phase 3: all threads: coalesced copy of the [SPB, ld] bf16 rows to HBM
+//   phase 2: one thread per (sample, basis direction): projection, then the L degrees     } ipe_encode_body.inc, shared with
+//   phase 3: all threads: coalesced copy of the [SPB, ld] bf16 rows to HBM                } ipe_from_gaussians_kernel (gaussians.hip)
+// The block geometry (samples per block, LDS pitch and size) is fe_block_geometry's (ipe_math.h), for both kernels.
 #include "common.h"
 
 // No floating-point contraction in this file: the instantiations of cast_rays_ipe_kernel (bf16 rows, f32 rows for the parity
@@ -23,12 +24,6 @@
 // explicit fmaf calls are fused in all).
 #pragma clang fp contract(off)
 
-#ifndef FE_THREADS                                     // (probe builds: -DFE_THREADS=... -DFE_STAGE_BYTES=..., tools/ipe_probe.py)
-#define FE_THREADS 256
-#endif
-#ifndef FE_STAGE_BYTES
-#define FE_STAGE_BYTES (32 * 1024)                      // feature rows a block stages in LDS
-#endif
 #include "ipe_math.h"
 
 // Tangents of the contraction for the density-gradient normals (models.py:445-446 applies warp_fn INSIDE predict_density, so
@@ -39,12 +34,7 @@
 //   dC[c]  = d cov' / d x_c = ku (du_c u^T + u du_c^T) + r_var (2 s ds_c I + dj2x_c x x^T + j2x (e_c x^T + x e_c^T))
 // with du_c = cc (x_c d + d_c x + (x.d) e_c) + 2 cc' x_c (x.d) x,  ds_c = cc x_c,  cc' = (3 sqrt(m) - 4) / m^3 and
 // dj2x_c = d(2 cc / sqrt(m))/dm * 2 x_c.  u itself comes from fe_gaussian's cancellation-free form.  Inside the unit ball the
-// contraction is the identity: dz[c] = e_c, dC = 0 (the no-warp case).
-struct FeTangent {
-  float dz[3][3];
-  float dC[3][6];          // xx, xy, xz, yy, yz, zz
-};
-
+// contraction is the identity: dz[c] = e_c, dC = 0 (the no-warp case).  (FeTangent: ipe_math.h.)
 __device__ __forceinline__ void fe_contract_tangent(const mnr_ipe_cfg& c, float t0, float t1, const float* o, const float* d,
                                                     float radius, FeTangent& T) {
 #pragma unroll
@@ -173,118 +163,7 @@ __global__ __launch_bounds__(FE_THREADS) void cast_rays_ipe_kernel(
   }
   __syncthreads();
 
-  const int row_elems = OUT_F32 ? nfeat : ld_feat;
-  // `pitch`: bytes between staged rows in LDS (row bytes + padding: with 1-KiB rows every sample of a wave hits the same banks).
-  // The kernel streams its feature rows out at 3.0-3.9 TB/s (1 GB per 64-sample proposal level in 0.27-0.36 ms).  That is NOT the
-  // write rate HBM sustains (a plain fill writes 6.9 TB/s, profiles/r5k_write_rate.txt): without its write-out the kernel takes 246 of
-  // its 357 us, without the encoding loop 191 (profiles/r5m_ipe_probe.txt): the two phases of a block barely overlap with the
-  // other blocks of its CU.  Round 2 cut the loop from ≈470 to ≈340 instructions per (sample, direction) without changing the
-  // time; round 5's two-directions-per-thread loop on v_pk_mul_f32 (1.7x fewer instructions, same bits) was 5-9 % SLOWER
-  // (profiles/r5n_probe.txt) and is not here.  The inner loop is short rather than clever:
-  // an anchor every 4th degree = one sin / cos of the wrapped argument (math.safe_sin's wrap at float32(100 pi),
-  // math.py:26-28; fe_sincos_wrapped) and one hardware exp2 for the attenuation; the 3 degrees behind it by the double-angle
-  // recurrence (sin 2x = 2 sin x cos x, cos 2x = 1 - 2 sin^2 x; cf. stable_pos_enc in the reference's tests/coord_test.py:34-43)
-  // and by att(l+1) = att(l)^4 (exp(-v 4^l / 2): two squarings): at most 3 steps of a ~1e-7 error, each at most x4.
-  // cos is the reference's sin(x + pi/2).  sin and cos feature of a (degree, direction) leave as one packed bf16 pair.
-  // TANGENT: three rows per sample (d/d mean_x, d/d mean_y, d/d mean_z), staged as [c][sample][ld].
-  const float inv_k = 1.0f / (float)K;
-#if defined(FE_DBG) && FE_DBG == 1                      // timing probe (tools/ipe_probe.py): no encoding (rows are whatever LDS holds)
-  for (int pair = threadIdx.x; pair < 0; pair += FE_THREADS) {
-#else
-  for (int pair = threadIdx.x; pair < ns * K; pair += FE_THREADS) {
-#endif
-    const int si = (int)(((float)pair + 0.5f) * inv_k);       // pair / K, exact for pair < 2^20
-    const int k = pair - si * K;
-    const FeSample g = gs[si];
-    const float px = bs[k * 3 + 0], py = bs[k * 3 + 1], pz = bs[k * 3 + 2];
-    // coord.py:131-132: mean . p_k ; p_k^T cov p_k.
-    const float lm = g.mean[0] * px + g.mean[1] * py + g.mean[2] * pz;
-    const float cx = g.cov[0] * px + g.cov[1] * py + g.cov[2] * pz;
-    const float cy = g.cov[1] * px + g.cov[3] * py + g.cov[4] * pz;
-    const float cz = g.cov[2] * px + g.cov[4] * py + g.cov[5] * pz;
-    const float lv = px * cx + py * cy + pz * cz;
-    const float vscale = -0.5f * 1.44269504088896340736f * lv;       // exp(-v/2) = exp2(vscale * 4^deg)
-    char* rowp = rows + (size_t)si * pitch + (size_t)k * (OUT_F32 ? 4 : (int)sizeof(bf16));       // column k of the sample's row (row 0 of 3 if TANGENT)
-    const int half = K * L * (OUT_F32 ? 4 : (int)sizeof(bf16));                      // byte offset of the cos half of the row
-    const int lstep = K * (OUT_F32 ? 4 : (int)sizeof(bf16));
-    float sc = ldexpf(1.0f, c.min_deg);                              // 2^deg, exact
-    float sn = 0.0f, cs = 1.0f, att = 1.0f;
-    float dlm[3] = {px, py, pz}, dlv[3] = {0.0f, 0.0f, 0.0f};
-    if (TANGENT) {
-      const FeTangent& T = gt[si];
-#pragma unroll
-      for (int cc = 0; cc < 3; ++cc) {
-        dlm[cc] = px * T.dz[cc][0] + py * T.dz[cc][1] + pz * T.dz[cc][2];
-        const float* C6 = T.dC[cc];
-        dlv[cc] = px * (C6[0] * px + C6[1] * py + C6[2] * pz) + py * (C6[1] * px + C6[3] * py + C6[4] * pz) +
-                  pz * (C6[2] * px + C6[4] * py + C6[5] * pz);
-      }
-    }
-    for (int l = 0; l < L; ++l) {
-      if ((l & 3) == 0) {
-        fe_sincos_wrapped(fe_wrap_100pi(lm * sc), &sn, &cs);
-        att = exp2f(vscale * sc * sc);
-      }
-      const float fs = att * sn;
-      const float fc = att * cs;
-      if (TANGENT) {
-        // d/d mean_c of att sin(lm 2^l) = att 2^l cos(.) dlm_c - 1/2 4^l att sin(.) dlv_c;  of att cos(.): -att 2^l sin(.) dlm_c
-        // - 1/2 4^l att cos(.) dlv_c, with dlm_c = p_k . dz[c], dlv_c = p_k^T dC[c] p_k (no warp: dlm_c = p_k[c], dlv_c = 0:
-        // the variance does not depend on the mean).
-        const float hv = -0.5f * sc * sc;
-#pragma unroll
-        for (int cc = 0; cc < 3; ++cc) {
-          char* rp = rowp + (size_t)cc * spb * pitch;
-          *(bf16*)rp = (bf16)(fc * sc * dlm[cc] + hv * fs * dlv[cc]);
-          *(bf16*)(rp + half) = (bf16)(-fs * sc * dlm[cc] + hv * fc * dlv[cc]);
-        }
-      } else if (OUT_F32) {
-        *(float*)rowp = fs;
-        *(float*)(rowp + half) = fc;
-      } else {
-        const f32x2 pr = {fs, fc};
-        const bf16x2 pb = __builtin_convertvector(pr, bf16x2);       // one v_cvt_pk_bf16_f32
-#if defined(FE_DBG) && FE_DBG == 4                      // timing probe: one LDS store per (sample, direction) instead of 2 L
-        if (l == L - 1) *(bf16x2*)(rows + (size_t)si * pitch + (size_t)k * 4) = pb;
-#else
-        *(bf16*)rowp = pb[0];
-        *(bf16*)(rowp + half) = pb[1];
-#endif
-      }
-      rowp += lstep;
-      const float s2 = 2.0f * sn * cs;
-      cs = 1.0f - 2.0f * sn * sn;
-      sn = s2;
-      const float a2 = att * att;
-      att = a2 * a2;
-      sc *= 2.0f;
-    }
-  }
-  if (!OUT_F32) {
-    // zero the padding columns [nfeat, ld)
-    const int pad = ld_feat - nfeat;
-    const int nrows = TANGENT ? 3 * spb : ns;
-    for (int e = threadIdx.x; e < nrows * pad; e += FE_THREADS) {
-      const int si = e / pad, cidx = nfeat + e % pad;
-      ((bf16*)(rows + (size_t)si * pitch))[cidx] = (bf16)0.0f;
-    }
-  }
-  __syncthreads();
-  // Coalesced write-out: the block's rows are contiguous in HBM (16 B per lane); in LDS they are `pitch` apart.
-  const int row_bytes = row_elems * (OUT_F32 ? 4 : (int)sizeof(bf16));
-  const int cpr = row_bytes >> 4;                         // 16-B chunks per row (row_bytes is a multiple of 16)
-  for (int cc = 0; cc < (TANGENT ? 3 : 1); ++cc) {
-    char* dst = (char*)feat_out + ((size_t)cc * total + s0) * row_bytes;
-    const char* src = rows + (size_t)cc * spb * pitch;
-#if defined(FE_DBG) && FE_DBG == 2                      // timing probe: no write-out (one chunk per block keeps the encoding alive)
-    for (int ch = threadIdx.x; ch < 1; ch += FE_THREADS) {
-#else
-    for (int ch = threadIdx.x; ch < ns * cpr; ch += FE_THREADS) {
-#endif
-      const int r = ch / cpr, o = (ch - r * cpr) << 4;
-      *(uint4*)(dst + (size_t)r * row_bytes + o) = *(const uint4*)(src + (size_t)r * pitch + o);
-    }
-  }
+#include "ipe_encode_body.inc"
 }
 
 static int fe_launch(int mode /*0 bf16, 1 f32, 2 tangent*/, const mnr_ipe_cfg* cfg, int64_t B, int n, const float* tdist, const float* origins,
@@ -293,34 +172,22 @@ static int fe_launch(int mode /*0 bf16, 1 f32, 2 tangent*/, const mnr_ipe_cfg* c
   MNR_CHECK_ARG(cfg && B > 0 && n > 0 && tdist && origins && directions && radii && basis && feat_out,
                 "mnr_cast_rays_ipe: null argument");
   MNR_CHECK_ARG(cfg->ray_shape == 0 || cfg->ray_shape == 1, "ray_shape must be 'cone' or 'cylinder'");  // render.py:124
-  const int K = cfg->basis_k, L = cfg->max_deg - cfg->min_deg;
-  MNR_CHECK_ARG(K >= 1 && K <= 128 && L >= 1 && L <= 32, "mnr_cast_rays_ipe: basis_k=%d / degrees=%d out of range", K, L);
-  const bool f32 = mode == 1;
-  const bool tangent = mode == 2;
-  const int nfeat = 2 * K * L;
-  const int row_elems = f32 ? nfeat : ld_feat;
-  MNR_CHECK_ARG(f32 || (ld_feat >= nfeat && ld_feat % 8 == 0), "mnr_cast_rays_ipe: ld_feat=%d must be >= %d and a multiple of 8", ld_feat, nfeat);
-  MNR_CHECK_ARG(!f32 || nfeat % 4 == 0, "mnr_cast_rays_ipe_f32: feature count must be a multiple of 4");
-  const size_t row_bytes = (size_t)row_elems * (f32 ? 4 : sizeof(bf16));
-  int spb = (int)(FE_STAGE_BYTES / (row_bytes * (tangent ? 3 : 1)));
-  if (spb > FE_THREADS) spb = FE_THREADS;
-  spb &= ~3;                       // keeps the row buffer 16-byte aligned behind the FeSample array
-  MNR_CHECK_ARG(spb >= 4, "mnr_cast_rays_ipe: feature row too long");
-  // 48 B of padding per staged row: consecutive samples then sit 12 banks apart (a wave covers ~3 samples x 21 directions)
-  const int pitch = (int)row_bytes + 48;
-  const size_t lds = (size_t)spb * (sizeof(FeSample) + (tangent ? sizeof(FeTangent) : 0)) + (size_t)((K * 3 + 3) & ~3) * 4 +
-                     (size_t)spb * pitch * (tangent ? 3 : 1);
+  // (gs_launch, gaussians.hip, also refuses a block that needs more than 64 KiB of LDS; this launch never has)
+  FeGeometry geo;
+  const int st = fe_block_geometry("mnr_cast_rays_ipe", "mnr_cast_rays_ipe_f32: feature count must be a multiple of 4", cfg, mode,
+                                   ld_feat, &geo);
+  if (st != MNR_OK) return st;
   const int64_t total = B * n;
-  const int grid = mnr_cdiv(total, spb);
-  if (tangent) {
-    hipLaunchKernelGGL((cast_rays_ipe_kernel<false, true>), dim3(grid), dim3(FE_THREADS), lds, (hipStream_t)stream, *cfg,
-                       total, n, spb, pitch, tdist, origins, directions, radii, basis, feat_out, ld_feat, means_out, covs_out);
-  } else if (f32) {
-    hipLaunchKernelGGL((cast_rays_ipe_kernel<true, false>), dim3(grid), dim3(FE_THREADS), lds, (hipStream_t)stream, *cfg,
-                       total, n, spb, pitch, tdist, origins, directions, radii, basis, feat_out, ld_feat, means_out, covs_out);
+  const dim3 grid(mnr_cdiv(total, geo.spb)), block(FE_THREADS);
+  if (mode == 2) {
+    hipLaunchKernelGGL((cast_rays_ipe_kernel<false, true>), grid, block, geo.lds, (hipStream_t)stream, *cfg, total, n, geo.spb,
+                       geo.pitch, tdist, origins, directions, radii, basis, feat_out, ld_feat, means_out, covs_out);
+  } else if (mode == 1) {
+    hipLaunchKernelGGL((cast_rays_ipe_kernel<true, false>), grid, block, geo.lds, (hipStream_t)stream, *cfg, total, n, geo.spb,
+                       geo.pitch, tdist, origins, directions, radii, basis, feat_out, ld_feat, means_out, covs_out);
   } else {
-    hipLaunchKernelGGL((cast_rays_ipe_kernel<false, false>), dim3(grid), dim3(FE_THREADS), lds, (hipStream_t)stream, *cfg,
-                       total, n, spb, pitch, tdist, origins, directions, radii, basis, feat_out, ld_feat, means_out, covs_out);
+    hipLaunchKernelGGL((cast_rays_ipe_kernel<false, false>), grid, block, geo.lds, (hipStream_t)stream, *cfg, total, n, geo.spb,
+                       geo.pitch, tdist, origins, directions, radii, basis, feat_out, ld_feat, means_out, covs_out);
   }
   MNR_CHECK_LAUNCH();
   return MNR_OK;
@@ -640,11 +507,8 @@ __global__ __launch_bounds__(FE_THREADS) void cast_rays_ipe_bwd_kernel(
     const int k = pair - si * K;
     const FeSample g = gs[si];
     const float px = bs[k * 3 + 0], py = bs[k * 3 + 1], pz = bs[k * 3 + 2];
-    const float lm = g.mean[0] * px + g.mean[1] * py + g.mean[2] * pz;
-    const float cx = g.cov[0] * px + g.cov[1] * py + g.cov[2] * pz;
-    const float cy = g.cov[1] * px + g.cov[3] * py + g.cov[4] * pz;
-    const float cz = g.cov[2] * px + g.cov[4] * py + g.cov[5] * pz;
-    const float lv = px * cx + py * cy + pz * cz;
+    float lm, lv;
+    fe_project(g, px, py, pz, &lm, &lv);
     const float vscale = -0.5f * 1.44269504088896340736f * lv;
     const float* grow = rows + (size_t)si * pitch + k;
     const int half = K * L;
@@ -652,20 +516,12 @@ __global__ __launch_bounds__(FE_THREADS) void cast_rays_ipe_bwd_kernel(
     float sn = 0.0f, cs = 1.0f, att = 1.0f;
     float g_lm = 0.0f, g_lv = 0.0f;
     for (int l = 0; l < L; ++l) {
-      if ((l & 3) == 0) {
-        fe_sincos_wrapped(fe_wrap_100pi(lm * sc), &sn, &cs);
-        att = exp2f(vscale * sc * sc);
-      }
+      if ((l & 3) == 0) fe_anchor(lm, vscale, sc, &sn, &cs, &att);
       const float fs = att * sn, fc = att * cs;
       const float gsn = grow[l * K], gcs = grow[half + l * K];
       g_lm += sc * (gsn * fc - gcs * fs);
       g_lv += -0.5f * sc * sc * (gsn * fs + gcs * fc);
-      const float s2 = 2.0f * sn * cs;
-      cs = 1.0f - 2.0f * sn * sn;
-      sn = s2;
-      const float a2 = att * att;
-      att = a2 * a2;
-      sc *= 2.0f;
+      fe_degree_step(&sn, &cs, &att, &sc);
     }
     part[(size_t)pair * 2] = g_lm;
     part[(size_t)pair * 2 + 1] = g_lv;
@@ -880,6 +736,7 @@ __global__ __launch_bounds__(FE_THREADS) void cast_rays_ipe_tangent_bwd_kernel(
     const FeSample g = gs[si];
     const FeTangent& T = gt[si];
     const float px = bs[k * 3 + 0], py = bs[k * 3 + 1], pz = bs[k * 3 + 2];
+    // (fe_project written out: through the helper hipcc orders this kernel differently, and the pinned device code is the validated one)
     const float lm = g.mean[0] * px + g.mean[1] * py + g.mean[2] * pz;
     const float cx = g.cov[0] * px + g.cov[1] * py + g.cov[2] * pz;
     const float cy = g.cov[1] * px + g.cov[3] * py + g.cov[4] * pz;
@@ -888,20 +745,12 @@ __global__ __launch_bounds__(FE_THREADS) void cast_rays_ipe_tangent_bwd_kernel(
     const float vscale = -0.5f * 1.44269504088896340736f * lv;
     float dlm[3], dlv[3];
 #pragma unroll
-    for (int cc = 0; cc < 3; ++cc) {
-      dlm[cc] = px * T.dz[cc][0] + py * T.dz[cc][1] + pz * T.dz[cc][2];
-      const float* C6 = T.dC[cc];
-      dlv[cc] = px * (C6[0] * px + C6[1] * py + C6[2] * pz) + py * (C6[1] * px + C6[3] * py + C6[4] * pz) +
-                pz * (C6[2] * px + C6[4] * py + C6[5] * pz);
-    }
+    for (int cc = 0; cc < 3; ++cc) fe_project_tangent(T, cc, px, py, pz, &dlm[cc], &dlv[cc]);
     float sc = ldexpf(1.0f, c.min_deg);
     float sn = 0.0f, cs = 1.0f, att = 1.0f;
     float g_lm = 0.0f, g_lv = 0.0f, g_dlm[3] = {0.0f, 0.0f, 0.0f}, g_dlv[3] = {0.0f, 0.0f, 0.0f};
     for (int l = 0; l < L; ++l) {
-      if ((l & 3) == 0) {
-        fe_sincos_wrapped(fe_wrap_100pi(lm * sc), &sn, &cs);
-        att = exp2f(vscale * sc * sc);
-      }
+      if ((l & 3) == 0) fe_anchor(lm, vscale, sc, &sn, &cs, &att);
       const float hv = -0.5f * sc * sc;
       const float aS = att * sn, aC = att * cs;
 #pragma unroll
@@ -919,12 +768,7 @@ __global__ __launch_bounds__(FE_THREADS) void cast_rays_ipe_tangent_bwd_kernel(
         g_dlm[cc] += sc * (gsn * aC - gcs * aS);
         g_dlv[cc] += hv * (gsn * aS + gcs * aC);
       }
-      const float s2 = 2.0f * sn * cs;
-      cs = 1.0f - 2.0f * sn * sn;
-      sn = s2;
-      const float a2 = att * att;
-      att = a2 * a2;
-      sc *= 2.0f;
+      fe_degree_step(&sn, &cs, &att, &sc);
     }
     float* pp = part + (size_t)pair * 8;
     pp[0] = g_lm;

@@ -807,11 +807,8 @@ __global__ __launch_bounds__(512) void mlp_chain_fwd_ipe_kernel(mnr_mlp_chain_fw
         }
         for (int si = r_lo + er0; si < r_hi; si += rpi) {
           const FeSample gsm = gs[si];
-          const float lm = gsm.mean[0] * px + gsm.mean[1] * py + gsm.mean[2] * pz;
-          const float cx = gsm.cov[0] * px + gsm.cov[1] * py + gsm.cov[2] * pz;
-          const float cy = gsm.cov[1] * px + gsm.cov[3] * py + gsm.cov[4] * pz;
-          const float cz = gsm.cov[2] * px + gsm.cov[4] * py + gsm.cov[5] * pz;
-          const float lv = px * cx + py * cy + pz * cz;
+          float lm, lv;
+          fe_project(gsm, px, py, pz, &lm, &lv);
           const float vscale = -0.5f * 1.44269504088896340736f * lv;
           float sc = sc0;
           float sn, cs;

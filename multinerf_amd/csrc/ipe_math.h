@@ -1,12 +1,23 @@
 // Per-sample Gaussian and trigonometric helpers of the integrated positional encoding, shared by the stand-alone
-// featurisation kernel (features.hip) and the fused chain's in-kernel layer-0 producer (fused_mlp.hip).
+// featurisation kernel of rays (features.hip), that of caller-supplied Gaussians (gaussians.hip) and the fused chain's in-kernel
+// layer-0 producer (fused_mlp.hip); the two featurisation kernels also share their block geometry (fe_block_geometry below)
+// and everything behind the per-sample Gaussian (ipe_encode_body.inc).
 //
-// Include it with floating-point contraction switched OFF (#pragma clang fp contract(off) in front of the include): both
-// users must evaluate the same separately rounded operations, or the features the fused chain builds in LDS stop being
-// bit-identical to the rows cast_rays_ipe_kernel writes (the explicit fmaf calls are fused in both).
+// Include it with floating-point contraction switched OFF (#pragma clang fp contract(off) in front of the include): all
+// users must evaluate the same separately rounded operations, or the features the fused chain builds in LDS and the rows of
+// ipe_from_gaussians_kernel stop being bit-identical to the rows cast_rays_ipe_kernel writes (the explicit fmaf calls are
+// fused in all).
 #pragma once
 
 #include "common.h"
+
+// Block size and LDS staging budget of cast_rays_ipe_kernel and ipe_from_gaussians_kernel.
+#ifndef FE_THREADS                                     // (probe builds: -DFE_THREADS=... -DFE_STAGE_BYTES=..., tools/ipe_probe.py)
+#define FE_THREADS 256
+#endif
+#ifndef FE_STAGE_BYTES
+#define FE_STAGE_BYTES (32 * 1024)                      // feature rows a block stages in LDS
+#endif
 
 #define FE_PI_2 1.57079632679489661923f
 #define FE_100PI 314.159265358979323846f
@@ -74,6 +85,80 @@ struct FeSample {
   float mean[3];
   float cov[6];   // xx, xy, xz, yy, yz, zz (symmetric)
 };
+
+// d z / d mean_c and d (J cov J^T) / d mean_c of the contraction, covariance held fixed (c = x, y, z): the tangents behind the
+// density-gradient normals.  Filled by fe_contract_tangent (features.hip: a ray's structured covariance) or gs_contract
+// (gaussians.hip: a general one); identity / zero without a contraction and inside the unit ball.
+struct FeTangent {
+  float dz[3][3];
+  float dC[3][6];          // xx, xy, xz, yy, yz, zz
+};
+
+// coord.py:131-132 for one basis direction p: lm = mean . p, lv = p^T cov p.
+__device__ __forceinline__ void fe_project(const FeSample& g, float px, float py, float pz, float* lm, float* lv) {
+  *lm = g.mean[0] * px + g.mean[1] * py + g.mean[2] * pz;
+  const float cx = g.cov[0] * px + g.cov[1] * py + g.cov[2] * pz;
+  const float cy = g.cov[1] * px + g.cov[3] * py + g.cov[4] * pz;
+  const float cz = g.cov[2] * px + g.cov[4] * py + g.cov[5] * pz;
+  *lv = px * cx + py * cy + pz * cz;
+}
+
+// The same for the tangent of mean component cc: dlm = p . dz[cc], dlv = p^T dC[cc] p.
+__device__ __forceinline__ void fe_project_tangent(const FeTangent& T, int cc, float px, float py, float pz, float* dlm, float* dlv) {
+  *dlm = px * T.dz[cc][0] + py * T.dz[cc][1] + pz * T.dz[cc][2];
+  const float* C6 = T.dC[cc];
+  *dlv = px * (C6[0] * px + C6[1] * py + C6[2] * pz) + py * (C6[1] * px + C6[3] * py + C6[4] * pz) +
+         pz * (C6[2] * px + C6[4] * py + C6[5] * pz);
+}
+
+// Anchor of the degree loop (every 4th degree): sin / cos of the wrapped argument lm 2^l and the attenuation
+// exp(-lv 4^l / 2) = exp2(vscale 4^l), sc = 2^l.
+__device__ __forceinline__ void fe_anchor(float lm, float vscale, float sc, float* sn, float* cs, float* att) {
+  fe_sincos_wrapped(fe_wrap_100pi(lm * sc), sn, cs);
+  *att = exp2f(vscale * sc * sc);
+}
+
+// One degree up: the double-angle recurrence, att(l+1) = att(l)^4, sc = 2^(l+1).
+__device__ __forceinline__ void fe_degree_step(float* sn, float* cs, float* att, float* sc) {
+  const float s2 = 2.0f * *sn * *cs;
+  *cs = 1.0f - 2.0f * *sn * *sn;
+  *sn = s2;
+  const float a2 = *att * *att;
+  *att = a2 * a2;
+  *sc *= 2.0f;
+}
+
+// Block geometry and the argument checks that go with it, for the launches of cast_rays_ipe_kernel (features.hip) and
+// ipe_from_gaussians_kernel (gaussians.hip): mode 0 = bf16 rows [ld_feat], 1 = fp32 rows [2KL], 2 = three bf16 tangent rows per
+// sample.  `who` names the entry in the messages; `f32_msg` is the whole refusal of fp32 rows that are no multiple of 16 bytes.
+struct FeGeometry {
+  int spb;        // samples per block
+  int pitch;      // bytes between staged rows in LDS
+  size_t lds;     // dynamic LDS bytes
+};
+
+static inline int fe_block_geometry(const char* who, const char* f32_msg, const mnr_ipe_cfg* cfg, int mode, int ld_feat,
+                                    FeGeometry* geo) {
+  const int K = cfg->basis_k, L = cfg->max_deg - cfg->min_deg;
+  MNR_CHECK_ARG(K >= 1 && K <= 128 && L >= 1 && L <= 32, "%s: basis_k=%d / degrees=%d out of range", who, K, L);
+  const bool f32 = mode == 1;
+  const bool tangent = mode == 2;
+  const int nfeat = 2 * K * L;
+  const int row_elems = f32 ? nfeat : ld_feat;
+  MNR_CHECK_ARG(f32 || (ld_feat >= nfeat && ld_feat % 8 == 0), "%s: ld_feat=%d must be >= %d and a multiple of 8", who, ld_feat, nfeat);
+  MNR_CHECK_ARG(!f32 || nfeat % 4 == 0, "%s", f32_msg);
+  const size_t row_bytes = (size_t)row_elems * (f32 ? 4 : sizeof(bf16));
+  int spb = (int)(FE_STAGE_BYTES / (row_bytes * (tangent ? 3 : 1)));
+  if (spb > FE_THREADS) spb = FE_THREADS;
+  spb &= ~3;                       // keeps the row buffer 16-byte aligned behind the FeSample array
+  MNR_CHECK_ARG(spb >= 4, "%s: feature row too long", who);
+  // 48 B of padding per staged row: consecutive samples then sit 12 banks apart (a wave covers ~3 samples x 21 directions)
+  geo->spb = spb;
+  geo->pitch = (int)row_bytes + 48;
+  geo->lds = (size_t)spb * (sizeof(FeSample) + (tangent ? sizeof(FeTangent) : 0)) + (size_t)((K * 3 + 3) & ~3) * 4 +
+             (size_t)spb * geo->pitch * (tangent ? 3 : 1);
+  return MNR_OK;
+}
 
 __device__ __forceinline__ void fe_gaussian(const mnr_ipe_cfg& c, float t0, float t1, const float* o,
                                             const float* d, float radius, FeSample& g) {

@@ -56,7 +56,7 @@ def _bits(t):
 def test_rows_equal_the_ray_kernels_bit_for_bit(ops, basis_name, maxdeg):
   """9 rays x 29 samples = 261 Gaussians (two blocks, the last one partial), warp_contract = False: the means and covariances
   mnr_cast_rays_ipe exports, fed back through mnr_ipe_from_gaussians, give its bf16 rows exactly (zero padding included), and
-  mnr_ipe_from_gaussians_tangent gives mnr_cast_rays_ipe_tangent's."""
+  mnr_ipe_from_gaussians_tangent gives mnr_cast_rays_ipe_tangent's; the unrounded fp32 rows are mnr_cast_rays_ipe_f32's."""
   gen = torch.Generator().manual_seed(31)
   B, n = 9, 29
   o = torch.rand((B, 3), generator=gen) * 2 - 1
@@ -83,6 +83,13 @@ def test_rows_equal_the_ray_kernels_bit_for_bit(ops, basis_name, maxdeg):
   np.testing.assert_allclose(mine_t.cpu().float().numpy(), tang.cpu().float().numpy(), atol=0, rtol=0)
   assert torch.equal(_bits(mine_t.cpu()), _bits(tang.cpu()))
   assert (mine_t.cpu().float()[:, nfeat:] == 0).all()
+  feat32 = ops.cast_rays_ipe_f32(dev(tdist), dev(o), dev(d), dev(radii), dev(basis), ray_shape='cone', warp_contract=False,
+                                 min_deg=0, max_deg=maxdeg)
+  _, mine32 = ops.ipe_from_gaussians(gm, gc, dev(basis), warp_contract=False, want_f32=True, **kw)
+  torch.cuda.synchronize()
+  assert mine32.shape == feat32.shape == (B * n, nfeat) and mine32.dtype == torch.float32
+  assert torch.equal(_bits(mine32.cpu()), _bits(feat32.cpu()))
+  assert feat32.abs().max().item() > 0.5
 
 
 # ----------------------------------------------------------------------------- (b), (c)

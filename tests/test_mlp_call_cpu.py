@@ -33,6 +33,24 @@ def test_source_file_is_on_every_build_list():
   assert '#pragma clang fp contract(off)' in src and '#include "ipe_math.h"' in src
 
 
+def test_encode_body_is_shared_not_copied():
+  """csrc/ipe_encode_body.inc is the one encode loop / write-out of both featurisation kernels, and is on the lists that
+  decide whether a built library is stale."""
+  inc = 'ipe_encode_body.inc'
+  assert os.path.join(build.CSRC, inc) in build.HEADERS
+  with open(os.path.join(ROOT, 'tools/hipsim/build.py')) as f:
+    assert "'%s'" % inc in f.read()
+  srcs = {}
+  for name in sorted(os.listdir(build.CSRC)):
+    with open(os.path.join(build.CSRC, name)) as f:
+      srcs[name] = f.read()
+  for name in ('features.hip', 'gaussians.hip'):
+    assert '#include "%s"' % inc in srcs[name], name
+  for gone in ('fe_sincos_wrapped', 'GsTangent', 'GS_THREADS'):
+    assert gone not in srcs['gaussians.hip'], gone
+  assert sum(text.count('struct FeTangent') for text in srcs.values()) == 1
+
+
 def test_mlp_of_an_unbuilt_model_raises():
   model = models.Model()
   g = (torch.zeros((1, 4, 3)), torch.zeros((1, 4, 3, 3)))
