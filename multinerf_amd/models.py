@@ -64,6 +64,63 @@ class Route:
     return self.chain or self.chain_trunk
 
 
+class _LevelBwd:
+  """What the stages of one `Model.backward_level` call share: the saved level `lv` with its plan, forward result `mlp` and route, the
+  row counts, the parameter and gradient vectors, and the panel-layout keywords of the trunk's GEMMs; its methods are the stages'
+  common buffers and VJP fragments."""
+
+  def __init__(self, model, lv, flat, grads, g_feat_out):
+    self.model, self.lv, self.flat, self.grads, self.g_feat_out = model, lv, flat, grads, g_feat_out
+    self.plan, self.mlp, self.M, self.n = lv['plan'], lv['mlp'], lv['M'], lv['n']
+    self.route: Route = self.mlp['route']
+    # Workspace of this pass, keyed by the stream it runs on: the proposal levels' backward runs on a side stream next to the
+    # NeRF level's (train_utils.create_train_step), and a proposal MLP that takes the per-layer path (not chain-eligible:
+    # non-ReLU activation, odd widths, MNR_FUSED_CHAIN=0) with the NeRF MLP's width and row count would otherwise share dA / dB /
+    # dV / dHB / ... with it.  Levels that run one after the other on the same stream share their buffers.
+    self.slot = 'nerf' if lv['level'] == model.num_levels - 1 else 'prop'
+    self.relu = self.plan.hp.net_activation == 'relu'
+    PAN, panel = ops.LAYOUT_PANEL, self.route.panel       # panel: the trunk's activations / masks / gradients are in panel storage
+    self.lay_c = dict(c_layout=PAN) if panel else {}
+    self.lay_ac = dict(a1_layout=PAN, c_layout=PAN) if panel else {}
+    self.tn_a = dict(a_layout=PAN) if panel else {}
+
+  def dy_buf(self, i):
+    """dY of trunk layer i's output: two ping-pong buffers shared by the levels of a stream."""
+    W, D = self.plan.W, len(self.plan.trunk)
+    return self.model._buf(('bwd', self.slot, 'dA' if (D - 1 - i) % 2 == 0 else 'dB', W), (self.M, W), bf16)
+
+  def dv_buf(self, i, nv):
+    WV = self.plan.hp.net_width_viewdirs
+    return self.model._buf(('bwd', self.slot, 'dV0' if (nv - 1 - i) % 2 == 0 else 'dV1', WV), (self.M, WV), bf16)
+
+  def gslice(self, off, size):
+    return self.grads[off:off + size]
+
+  def act_vjp(self, z, d):
+    """Non-ReLU activations: d (gradient w.r.t. a layer's activation, just written without a mask) *= act'(z)."""
+    if not self.relu:
+      ops.act_bwd(self.plan.hp.net_activation, z, d)
+
+  def mask_kw(self, i):
+    """ReLU VJP of trunk layer i's output: 1-bit mask if available, else the saved activation."""
+    if not self.relu:
+      return {}
+    if self.mlp['bits'][i] is not None:
+      return dict(bits_in=self.mlp['bits'][i])
+    return dict(mask=self.mlp['acts'][i], ldmask=self.plan.W)
+
+  def feat_grad(self, i, dy, dy_panel=False):
+    """d loss / d features through trunk layer i (0 or a skip layer): dY_i @ kernel_i[feature rows]^T -> bf16 [M, ldF]."""
+    if self.g_feat_out is None:
+      return
+    plan, M = self.plan, self.M
+    e_ = plan.packed[('trunk', i)]
+    out = self.model._buf(('bwd', self.slot, 'g_feat', len(self.g_feat_out)), (M, plan.ldF), bf16)
+    ops.gemm_nt(dy, self.model._w(plan, e_['bf_off'], plan.ldF, e_['bf_ld']), M=M, N=plan.ldF, K1=e_['bf_ld'], Cb=out,
+                ldcb=plan.ldF, nb=plan.ldF, **(dict(a1_layout=ops.LAYOUT_PANEL) if dy_panel else {}))
+    self.g_feat_out.append(out)
+
+
 # Module-level switches of the host orchestration.  Every one of them was a same-box A/B in rounds 2-4 (profiles/HISTORY.md,
 # profiles/r4_ab.md) and is settled; they stay as plain constants because the bitwise / parity tests compare the two forms of
 # each (tests/test_gpu_chain.py, tests/test_sim_model.py set them on the module).  The environment is not read.
@@ -943,39 +1000,28 @@ class Model:
                           out=feat)
       bnoise = None
       if randomized and plan.has_rgb and plan.use_viewdirs and hp.bottleneck_noise > 0:      # models.py:530-533
-        bw_ = hp.bottleneck_width                                  # (the execution layout's; bw_t: the configuration's)
-        bw_t = self._tplans[self._plans.index(plan)].hp.bottleneck_width
+        given = None
         if noise is not None and 'bottleneck_noise' in noise:
-          bnoise = noise['bottleneck_noise'][i_level].to(dev).reshape(-1, n, bw_t).float()
-          if bnoise.shape[0] != Bp:
-            bnoise = torch.cat([bnoise, bnoise[-1:].expand(Bp - bnoise.shape[0], n, bw_t)], 0)
-          bnoise = bnoise.reshape(M, bw_t)
-        else:
-          bnoise = torch.randn((M, bw_t), generator=gen, device=dev, dtype=f32)
-        if bw_ != bw_t:                                             # padded bottleneck columns (they feed zero kernel rows): no noise
-          bnoise = torch.cat([bnoise, bnoise.new_zeros((M, bw_ - bw_t))], 1)
-        bnoise = bnoise.contiguous()
+          bw_t = self._bottleneck_true(plan)
+          given = noise['bottleneck_noise'][i_level].to(dev).reshape(-1, n, bw_t).float()
+          if given.shape[0] != Bp:
+            given = torch.cat([given, given[-1:].expand(Bp - given.shape[0], n, bw_t)], 0)
+          given = given.reshape(M, bw_t)
+        bnoise = self._bottleneck_noise(plan, M, given, gen).contiguous()
       if route.ipe:
         mlp_out = self._chain_forward_ipe(plan, route, flat, tdist, R, radii, M, tag)
       else:
         mlp_out = self._mlp_forward(plan, route, flat, feat, M, n, R, tag, keep_for_backward, tdist=tdist, bnoise=bnoise,
-                                    group=group)
+                                    group=group, glo_table=self._glo_table(flat) if plan.glo > 0 else None, glo_cam=self._glo_cam)
 
       # --- density noise (models.py:462-464), background colour (:241-254)
       dnoise = None
       if randomized and hp.density_noise > 0:
-        if noise is not None and 'density_noise' in noise:
-          dnoise = noise['density_noise'][i_level].to(dev).float()
-          dnoise = dnoise.reshape(1, 1).expand(Bp, n) if dnoise.numel() == 1 else dnoise.reshape(-1, n)
-          if dnoise.shape[0] != Bp:
-            dnoise = torch.cat([dnoise, dnoise[-1:].expand(Bp - dnoise.shape[0], n)], 0)
-          dnoise = dnoise.contiguous()
-        else:
-          # with density-gradient normals the reference draws inside vmap(value_and_grad(predict_density)) (models.py:462-464 under
-          # :478-481) from a key that is closed over, not mapped: every sample of the level gets the SAME value
-          # (tests/golden/make_golden_models.py, case llff_raw_dn)
-          dnoise = (torch.randn((1, 1), generator=gen, device=dev, dtype=f32).expand(Bp, n).contiguous() if plan.tangent
-                    else torch.randn((Bp, n), generator=gen, device=dev, dtype=f32))
+        given = noise['density_noise'][i_level] if noise is not None and 'density_noise' in noise else None
+        dnoise = self._density_noise(plan, Bp, n, given, gen)
+        if dnoise.shape[0] != Bp:
+          dnoise = torch.cat([dnoise, dnoise[-1:].expand(Bp - dnoise.shape[0], n)], 0)
+        dnoise = dnoise.contiguous()
       lo, hi = self.bg_intensity_range
       bg = None
       if lo == hi:
@@ -991,12 +1037,7 @@ class Model:
         else:
           u = torch.rand((Bp, 3), generator=gen, device=dev, dtype=f32)
         bg = (lo + (hi - lo) * u).contiguous()
-      ccfg = ops.composite_cfg(n, opaque_background=self.opaque_background, density_act=hp.density_activation,
-                               density_bias=hp.density_bias, density_noise_std=hp.density_noise if dnoise is not None else 0.0,
-                               has_rgb=plan.has_rgb, rgb_act='identity' if plan.diffuse_on else hp.rgb_activation,
-                               rgb_premultiplier=1.0 if plan.diffuse_on else hp.rgb_premultiplier,
-                               rgb_bias=0.0 if plan.diffuse_on else hp.rgb_bias,
-                               rgb_padding=0.0 if plan.diffuse_on else hp.rgb_padding, bg_mode=bg_mode, bg_value=bg_value)
+      ccfg = self._composite_cfg(plan, n, dnoise is not None, self.opaque_background, bg_mode, bg_value)
       raw_density = mlp_out['raw_density'].view(Bp, n)
       raw_rgb = mlp_out['raw_rgb'].view(Bp, n, 3) if plan.has_rgb else None
       density, rgb, weights, rgb_out, acc = ops.composite_fwd(
@@ -1212,133 +1253,194 @@ class Model:
     return T_feat, T_acts, raw_grad, T_pre
 
   def _mlp_forward(self, plan: MLPPlan, route: Route, flat, feat, M, n, R, tag, keep, tdist=None, bnoise=None, group=None,
-                   T_feat=None):
-    """MLP.__call__ (models.py:402-612) for the M = B*n samples of one level on the route `_route(plan, M, keep)` gave.
+                   T_feat=None, glo_table=None, glo_cam=None):
+    """MLP.__call__ (models.py:402-612) for the M = B*n samples of one level on the route `_route(plan, M, keep)` gave: trunk,
+    head (by kind), tangent network, colour branch.
     `T_feat`: pre-built tangent rows for the density-gradient normals (`mlp_call`: the caller's Gaussians have no ray to cast);
-    None = cast them from the rays."""
-    hp = plan.hp
+    None = cast them from the rays.  glo_table [rows, G] / glo_cam [B] int32: the GLO vectors and each ray's row of them."""
     if route.chain:
       return self._chain_forward(plan, route, flat, feat, M, tag, keep, group)
     assert group is None
-    relu = hp.net_activation == 'relu'
-    act = None if relu else hp.net_activation
-    chain, need_bits = route.chain_trunk, route.need_bits
-    acts, bits, zs, vzs = [], [], [], []
-    x = None
-    # panel layout for the trunk of this level (the layout of acts / bits / every trunk dY of the backward pass): every
-    # producer and consumer is then a panel-aware GEMM, which the plain merged head of a wide ReLU trunk guarantees
-    panel = route.panel
-    PAN = ops.LAYOUT_PANEL
-    lay_c = dict(c_layout=PAN) if panel else {}
-    lay_a = dict(a1_layout=PAN) if panel else {}
-
-    def activate(z_key, out, n_cols, zlist):
-      """Non-ReLU net_activation: the GEMM wrote the pre-activation into `out`'s twin buffer; apply act (models.py:457,578)."""
-      z = self._buf(z_key, (M, n_cols), bf16)
-      zlist.append(z)
-      return z
-
-    if chain:
-      acts, bits = self._chain_trunk(plan, flat, feat, M, tag, keep, need_bits)
-      x = acts[-1]
-    for i, (d, concat) in enumerate([] if chain else plan.trunk):
-      out = self._buf((tag, 'act', i if keep else i % 2), (M, plan.W), bf16)
-      # 1-bit ReLU mask: backward pass (training) and the tangent pass of the density-gradient normals
-      bo = self._buf((tag, 'bits', i if (keep or plan.tangent) else i % 2), (M, plan.W // 8), torch.uint8) if need_bits else None
-      bits.append(bo)
-      dst = out if relu else activate((tag, 'z', i if (keep or plan.tangent) else i % 2), out, plan.W, zs)
-      # (layer 0 reads the row-major features; the layers above it the trunk's own layout)
-      self._dense_fwd(feat if i == 0 else x, feat if concat else None, self._fw(plan, ('trunk', i)), dst, M, act, out,
-                      bias=d.bias(flat), n_bias=d.fan_out, relu=relu, bits_out=bo, walk_descending=bool(i & 1),
-                      **({} if i == 0 else lay_a), **lay_c)
-      acts.append(out)
-      x = out
-    res = self._mlp_result(route, acts=acts, bits=bits, zs=zs, vzs=vzs)
+    acts, bits, zs = self._trunk_forward(plan, route, flat, feat, M, tag, keep)
+    x = acts[-1]
+    res = self._mlp_result(route, acts=acts, bits=bits, zs=zs, vzs=[])
     raw_density = self._buf((tag, 'raw_density'), (M,), f32)
-    if plan.has_rgb and not plan.use_viewdirs:
-      # models.py:585 with x = the trunk output: one 4-column head [raw_density | raw_rgb] as an fp32 side output
-      Bt = self._fw(plan, 'head4')
-      small4 = self._buf((tag, 'small4'), (M, 4), f32)
-      ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.head_bias, n_bias=4, relu=False, Cf=small4, ldcf=4, f0=0, nf=4)
-      raw_density.copy_(small4[:, 0])
-      raw_rgb = self._buf((tag, 'raw_rgb'), (M, 3), f32)
-      raw_rgb.copy_(small4[:, 1:4])
-      res.update(raw_rgb=raw_rgb, raw_density=raw_density)
-      return res
-    if plan.has_rgb:
-      bw = hp.bottleneck_width
+
+    def tangent():
+      out = self._tangent_forward(plan, route, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
+      return dict(zip(('T_feat', 'T_acts', 'raw_grad', 'T_pre'), out))
+
+    if not plan.has_rgb:
+      Bt = self._fw(plan, 'density')
+      ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.density.bias(flat), n_bias=1, relu=False, Cf=raw_density, ldcf=1, f0=0, nf=1)
+    elif not plan.use_viewdirs:
+      res['raw_rgb'] = self._head4_forward(plan, x, M, tag, raw_density)
+    else:
       VI = self._buf((tag, 'VI'), (M, plan.ldVI), bf16)
-      Bt = self._fw(plan, 'head')
-      nh = Bt.shape[0]
       if plan.ref:
-        small = self._buf((tag, 'small'), (M, 11), f32)
-        ops.gemm_nt(x, Bt, M=M, N=nh, K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
-                    Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=small, ldcf=11, f0=bw, nf=11)
-        raw_density.copy_(small[:, 0])
-        raw_grad = None
-        if plan.tangent:
-          T_feat, T_acts, raw_grad, T_pre = self._tangent_forward(plan, route, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
-          res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, T_pre=T_pre)
-        normals, npred, rough = ops.ref_head_fwd(small, raw_grad, R.viewdirs, n, plan.ide, hp.roughness_bias, VI,
-                                                 bw, plan.ldVI, features=plan.features, deg_view=hp.deg_view)
-        res.update(small=small, normals=normals, npred=npred, rough=rough)
+        res.update(self._ref_head_forward(plan, x, VI, raw_density, M, n, R, tag, tangent))
       elif plan.pn:
-        # [raw_density | grad_pred] as the fp32 side output; normals_pred = -l2_normalize(grad_pred) (models.py:494-503)
-        small = self._buf((tag, 'small_pn'), (M, 4), f32)
-        ops.gemm_nt(x, Bt, M=M, N=nh, K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
-                    Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=small, ldcf=4, f0=bw, nf=4, **lay_a)
-        raw_density.copy_(small[:, 0])
-        ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
-        res.update(small=small, npred=ops.pred_normals_fwd(small, 1))
-      elif route.vcol:
-        # the plain merged head [bottleneck | density] behind a panel-storage trunk: N = 256 and the density column as a VECTOR
-        # (row bw of the merged forward image) instead of a second 256-column tile for one column (mnr_gemm_nt_args.vcol:
-        # one extra MFMA per wave and k-step; bitwise the merged operand's result)
-        ops.gemm_nt(x, Bt[:bw], M=M, N=bw, K1=plan.W, bias=plan.head_bias, n_bias=bw, relu=False, Cb=VI, ldcb=plan.ldVI, nb=bw,
-                    vcol=Bt[bw], vcol_out=raw_density, vcol_bias=plan.head_bias[bw:bw + 1], **lay_a)
-        ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
+        res.update(self._pn_head_forward(plan, route, x, VI, raw_density, M, n, R, tag))
       else:
-        ops.gemm_nt(x, Bt, M=M, N=nh, K1=plan.W, bias=plan.head_bias, n_bias=bw + 1, relu=False,
-                    Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=raw_density, ldcf=1, f0=bw, nf=1, **lay_a)
-        ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
+        self._plain_head_forward(plan, route, x, VI, raw_density, M, n, R)
       if plan.dn:
         # density-gradient normals without the rest of the Ref-NeRF head (models.py:478-492): for the renderings and the
         # orientation loss; they do not enter the colour
-        T_feat, T_acts, raw_grad, T_pre = self._tangent_forward(plan, route, tdist, R, M, bits, keep, tag, zs=zs, T_feat=T_feat)
-        res.update(T_feat=T_feat, T_acts=T_acts, raw_grad=raw_grad, normals=ops.density_normals_fwd(raw_grad), T_pre=T_pre)
-      if plan.glo > 0:
-        # (`mlp_call` feeds the caller's glo_vec as a table of its own, one row per ray)
-        glo_table = getattr(R, 'glo_table', None)
-        ops.glo_fill(self._glo_table(flat) if glo_table is None else glo_table, self._glo_cam, M // n, n, VI, plan.glo_col)
-      if bnoise is not None:
-        # bottleneck += bottleneck_noise * N(0, 1) (models.py:530-533): additive, so the backward pass is unchanged
-        ops.add_noise_bf16(VI, bw, bnoise, hp.bottleneck_noise)
-      h = VI
-      vacts, vbits = [], []
-      WV = hp.net_width_viewdirs
-      for i, (d, concat) in enumerate(plan.view):
-        out = self._buf((tag, 'vact', i if keep else i % 2), (M, WV), bf16)
-        dst = out if relu else activate((tag, 'vz', i if keep else i % 2), out, WV, vzs)
-        self._dense_fwd(h, VI if concat else None, self._fw(plan, ('view', i)), dst, M, act, out, bias=d.bias(flat),
-                        n_bias=d.fan_out, relu=relu)
-        vacts.append(out)
-        h = out
-      raw_rgb = self._buf((tag, 'raw_rgb'), (M, 3), f32)
-      Bt = self._fw(plan, 'rgb')
-      ops.gemm_nt(h, Bt, M=M, N=Bt.shape[0], K1=Bt.shape[1], bias=plan.rgb.bias(flat), n_bias=3, relu=False, Cf=raw_rgb, ldcf=3,
-                  f0=0, nf=3)
-      res.update(VI=VI, vacts=vacts, raw_rgb=raw_rgb)
-      if plan.diffuse_on:
-        # models.py:584-602: tinted (or halved) specular + diffuse, tone-mapped; compositing then sees final colours
-        res['raw_rgb_pre'] = raw_rgb
-        res['raw_rgb'] = ops.ref_color_fwd(raw_rgb, res['small'], hp.rgb_premultiplier, hp.rgb_bias, hp.rgb_padding,
-                                           hp.use_specular_tint)
-    else:
-      Bt = self._fw(plan, 'density')
-      ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.density.bias(flat), n_bias=1, relu=False, Cf=raw_density, ldcf=1,
-                  f0=0, nf=1)
+        t = tangent()
+        res.update(t, normals=ops.density_normals_fwd(t['raw_grad']))
+      res.update(self._color_forward(plan, flat, VI, M, n, tag, keep, bnoise, glo_table, glo_cam, res.get('small')))
     res['raw_density'] = raw_density
     return res
+
+  def _trunk_forward(self, plan: MLPPlan, route: Route, flat, feat, M, tag, keep):
+    """models.py:455-459, the Dense + activation trunk with its skip concat, as the fused chain (`_chain_trunk`) or one GEMM per
+    layer -> (acts, bits, zs): every layer's activation when `keep`, else at least the last one (the heads' input); the 1-bit
+    ReLU masks where the route asks for them; the pre-activations of a non-ReLU net."""
+    if route.chain_trunk:
+      return self._chain_trunk(plan, flat, feat, M, tag, keep, route.need_bits) + ([],)
+    relu = plan.hp.net_activation == 'relu'
+    # panel layout for the trunk of this level (the layout of acts / bits / every trunk dY of the backward pass): every
+    # producer and consumer is then a panel-aware GEMM, which the plain merged head of a wide ReLU trunk guarantees
+    lay_c = dict(c_layout=ops.LAYOUT_PANEL) if route.panel else {}
+    lay_a = dict(a1_layout=ops.LAYOUT_PANEL) if route.panel else {}
+    acts, bits, zs = [], [], []
+    x = None
+    for i, (d, concat) in enumerate(plan.trunk):
+      out = self._buf((tag, 'act', i if keep else i % 2), (M, plan.W), bf16)
+      # 1-bit ReLU mask: backward pass (training) and the tangent pass of the density-gradient normals
+      bo = self._buf((tag, 'bits', i if (keep or plan.tangent) else i % 2), (M, plan.W // 8), torch.uint8) if route.need_bits else None
+      bits.append(bo)
+      dst = out
+      if not relu:               # the GEMM writes the pre-activation, `_dense_fwd` applies the activation (models.py:457)
+        dst = self._buf((tag, 'z', i if (keep or plan.tangent) else i % 2), (M, plan.W), bf16)
+        zs.append(dst)
+      # (layer 0 reads the row-major features; the layers above it the trunk's own layout)
+      self._dense_fwd(feat if i == 0 else x, feat if concat else None, self._fw(plan, ('trunk', i)), dst, M,
+                      None if relu else plan.hp.net_activation, out, bias=d.bias(flat), n_bias=d.fan_out, relu=relu, bits_out=bo,
+                      walk_descending=bool(i & 1), **({} if i == 0 else lay_a), **lay_c)
+      acts.append(out)
+      x = out
+    return acts, bits, zs
+
+  def _head4_forward(self, plan: MLPPlan, x, M, tag, raw_density):
+    """use_viewdirs = False (models.py:585 with x = the trunk output): one 4-column head [raw_density | raw_rgb] as an fp32 side
+    output; fills raw_density -> raw_rgb."""
+    Bt = self._fw(plan, 'head4')
+    small4 = self._buf((tag, 'small4'), (M, 4), f32)
+    ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.head_bias, n_bias=4, relu=False, Cf=small4, ldcf=4, f0=0, nf=4)
+    raw_density.copy_(small4[:, 0])
+    raw_rgb = self._buf((tag, 'raw_rgb'), (M, 3), f32)
+    raw_rgb.copy_(small4[:, 1:4])
+    return raw_rgb
+
+  def _ref_head_forward(self, plan: MLPPlan, x, VI, raw_density, M, n, R, tag, tangent):
+    """The Ref-NeRF head (models.py:512-563): the merged head GEMM (bottleneck -> VI, 11 fp32 side columns), the tangent network
+    where the normals are the density's gradient, then directions / IDE / n.v into VI -> its entries of the MLP result."""
+    hp, bw, Bt = plan.hp, plan.hp.bottleneck_width, self._fw(plan, 'head')
+    small = self._buf((tag, 'small'), (M, 11), f32)
+    ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
+                Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=small, ldcf=11, f0=bw, nf=11)
+    raw_density.copy_(small[:, 0])
+    out = tangent() if plan.tangent else {}
+    normals, npred, rough = ops.ref_head_fwd(small, out.get('raw_grad'), R.viewdirs, n, plan.ide, hp.roughness_bias, VI,
+                                             bw, plan.ldVI, features=plan.features, deg_view=hp.deg_view)
+    out.update(small=small, normals=normals, npred=npred, rough=rough)
+    return out
+
+  def _pn_head_forward(self, plan: MLPPlan, route: Route, x, VI, raw_density, M, n, R, tag):
+    """The merged head with predicted normals only: [raw_density | grad_pred] as the fp32 side output; normals_pred =
+    -l2_normalize(grad_pred) (models.py:494-503) -> its entries of the MLP result."""
+    hp, bw, Bt = plan.hp, plan.hp.bottleneck_width, self._fw(plan, 'head')
+    small = self._buf((tag, 'small_pn'), (M, 4), f32)
+    ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.head_bias, n_bias=plan.head_cols, relu=False,
+                Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=small, ldcf=4, f0=bw, nf=4, **(dict(a1_layout=ops.LAYOUT_PANEL) if route.panel else {}))
+    raw_density.copy_(small[:, 0])
+    ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
+    return dict(small=small, npred=ops.pred_normals_fwd(small, 1))
+
+  def _plain_head_forward(self, plan: MLPPlan, route: Route, x, VI, raw_density, M, n, R):
+    """The plain merged head [bottleneck | density] (models.py:460,527) and the view direction's encoding into VI."""
+    hp, bw, Bt = plan.hp, plan.hp.bottleneck_width, self._fw(plan, 'head')
+    lay_a = dict(a1_layout=ops.LAYOUT_PANEL) if route.panel else {}
+    if route.vcol:
+      # behind a panel-storage trunk: N = 256 and the density column as a VECTOR (row bw of the merged forward image) instead
+      # of a second 256-column tile for one column (mnr_gemm_nt_args.vcol: one extra MFMA per wave and k-step; bitwise the
+      # merged operand's result)
+      ops.gemm_nt(x, Bt[:bw], M=M, N=bw, K1=plan.W, bias=plan.head_bias, n_bias=bw, relu=False, Cb=VI, ldcb=plan.ldVI, nb=bw,
+                  vcol=Bt[bw], vcol_out=raw_density, vcol_bias=plan.head_bias[bw:bw + 1], **lay_a)
+    else:
+      ops.gemm_nt(x, Bt, M=M, N=Bt.shape[0], K1=plan.W, bias=plan.head_bias, n_bias=bw + 1, relu=False,
+                  Cb=VI, ldcb=plan.ldVI, nb=bw, Cf=raw_density, ldcf=1, f0=bw, nf=1, **lay_a)
+    ops.viewdir_enc_fill(R.viewdirs, n, hp.deg_view, VI, bw, plan.ldVI)
+
+  def _color_forward(self, plan: MLPPlan, flat, VI, M, n, tag, keep, bnoise=None, glo_table=None, glo_cam=None, small=None):
+    """The colour branch (models.py:530-533,565-602), the forward of `_color_bwd`: the view MLP and the rgb Dense(3) on the view
+    input VI [M, ldVI], whose bottleneck and direction columns the head stage wrote.  Into VI first: the GLO vectors
+    glo_table[glo_cam[ray]] (zeros without glo_cam) where the MLP reads them, and bnoise [M, bottleneck] scaled by bottleneck_noise
+    onto the bottleneck.  small: the Ref-NeRF head's side columns (diffuse colour, tint).
+    -> dict(VI, vacts, vzs, raw_rgb) and, with a diffuse colour, raw_rgb_pre (the rgb Dense's output; raw_rgb is then the final colour)."""
+    hp, bw, WV = plan.hp, plan.hp.bottleneck_width, plan.hp.net_width_viewdirs
+    relu = hp.net_activation == 'relu'
+    if plan.glo > 0:
+      ops.glo_fill(glo_table, glo_cam, M // n, n, VI, plan.glo_col)
+    if bnoise is not None:
+      # bottleneck += bottleneck_noise * N(0, 1) (models.py:530-533): additive, so the backward pass is unchanged
+      ops.add_noise_bf16(VI, bw, bnoise, hp.bottleneck_noise)
+    h = VI
+    vacts, vzs = [], []
+    for i, (d, concat) in enumerate(plan.view):
+      out = dst = self._buf((tag, 'vact', i if keep else i % 2), (M, WV), bf16)
+      if not relu:                                         # (pre-activation and activation as in `_trunk_forward`, models.py:578)
+        dst = self._buf((tag, 'vz', i if keep else i % 2), (M, WV), bf16)
+        vzs.append(dst)
+      self._dense_fwd(h, VI if concat else None, self._fw(plan, ('view', i)), dst, M, None if relu else hp.net_activation, out,
+                      bias=d.bias(flat), n_bias=d.fan_out, relu=relu)
+      vacts.append(out)
+      h = out
+    raw_rgb = self._buf((tag, 'raw_rgb'), (M, 3), f32)
+    Bt = self._fw(plan, 'rgb')
+    ops.gemm_nt(h, Bt, M=M, N=Bt.shape[0], K1=Bt.shape[1], bias=plan.rgb.bias(flat), n_bias=3, relu=False, Cf=raw_rgb, ldcf=3, f0=0, nf=3)
+    res = dict(VI=VI, vacts=vacts, vzs=vzs, raw_rgb=raw_rgb)
+    if plan.diffuse_on:
+      # models.py:584-602: tinted (or halved) specular + diffuse, tone-mapped; compositing then sees final colours
+      res.update(raw_rgb_pre=raw_rgb, raw_rgb=ops.ref_color_fwd(raw_rgb, small, hp.rgb_premultiplier, hp.rgb_bias, hp.rgb_padding,
+                                                                hp.use_specular_tint))
+    return res
+
+  def _bottleneck_true(self, plan: MLPPlan):
+    """The configuration's bottleneck_width (plan.hp holds the execution layout's, `build`)."""
+    return self._tplans[self._plans.index(plan)].hp.bottleneck_width
+
+  def _bottleneck_noise(self, plan: MLPPlan, rows, given, gen):
+    """models.py:530-533: the N(0, 1) rows [rows, bottleneck] of `_color_forward`, `given` [rows, the configuration's width] or
+    drawn from `gen`; the padded bottleneck columns (they feed zero kernel rows) get no noise."""
+    bw, bw_t = plan.hp.bottleneck_width, self._bottleneck_true(plan)
+    b = given if given is not None else torch.randn((rows, bw_t), generator=gen, device=self.device, dtype=f32)
+    return b if bw == bw_t else torch.cat([b, b.new_zeros((rows, bw - bw_t))], 1)
+
+  def _density_noise(self, plan: MLPPlan, B, n, given, gen):
+    """models.py:462-464: the N(0, 1) values [B, n] added to raw_density, `given` (one value, or one per sample: then as many
+    rows as it has) or drawn from `gen`."""
+    dev = self.device
+    if given is not None:
+      given = given.to(dev).float()
+      return given.reshape(1, 1).expand(B, n) if given.numel() == 1 else given.reshape(-1, n)
+    if plan.tangent:
+      # with density-gradient normals the reference draws inside vmap(value_and_grad(predict_density)) (models.py:462-464 under
+      # :478-481) from a key that is closed over, not mapped: every sample of the level gets the SAME value
+      # (tests/golden/make_golden_models.py, case llff_raw_dn)
+      return torch.randn((1, 1), generator=gen, device=dev, dtype=f32).expand(B, n)
+    return torch.randn((B, n), generator=gen, device=dev, dtype=f32)
+
+  def _composite_cfg(self, plan: MLPPlan, n, noisy, opaque_background, bg_mode, bg_value):
+    """mnr_composite_fwd / mnr_level_bwd's configuration for `plan` on n samples per row.  With a diffuse colour the MLP hands
+    over final colours (`_color_forward`), so the rgb activation is the identity."""
+    hp, final = plan.hp, plan.diffuse_on
+    return ops.composite_cfg(n, opaque_background=opaque_background, density_act=hp.density_activation, density_bias=hp.density_bias,
+                             density_noise_std=hp.density_noise if noisy else 0.0, has_rgb=plan.has_rgb,
+                             rgb_act='identity' if final else hp.rgb_activation, rgb_premultiplier=1.0 if final else hp.rgb_premultiplier,
+                             rgb_bias=0.0 if final else hp.rgb_bias, rgb_padding=0.0 if final else hp.rgb_padding, bg_mode=bg_mode,
+                             bg_value=bg_value)
 
   def _head_gcol(self, plan: MLPPlan):
     """The merged head's weight gradient as the bottleneck's 256-column GEMM plus the density column as a vector (backward_level)."""
@@ -1475,27 +1577,12 @@ class Model:
     if rng is not None:
       gen = rng if isinstance(rng, torch.Generator) else torch.Generator(device=dev).manual_seed(int(rng))
     bnoise = None
-    if randomized and plan.has_rgb and plan.use_viewdirs and hp.bottleneck_noise > 0:      # models.py:530-533, as `_forward`
-      bw_ = hp.bottleneck_width
-      bw_t = self._tplans[self._plans.index(plan)].hp.bottleneck_width
-      if 'bottleneck_noise' in nz:
-        bnoise = nz['bottleneck_noise'].to(dev).float().reshape(M0, bw_t)
-      elif gen is not None:
-        bnoise = torch.randn((M0, bw_t), generator=gen, device=dev, dtype=f32)
-      if bnoise is not None:
-        if bw_ != bw_t:
-          bnoise = torch.cat([bnoise, bnoise.new_zeros((M0, bw_ - bw_t))], 1)
-        bnoise = rows(bnoise, bw_)
+    if randomized and plan.has_rgb and plan.use_viewdirs and hp.bottleneck_noise > 0 and ('bottleneck_noise' in nz or gen is not None):
+      given = nz['bottleneck_noise'].to(dev).float().reshape(M0, self._bottleneck_true(plan)) if 'bottleneck_noise' in nz else None
+      bnoise = rows(self._bottleneck_noise(plan, M0, given, gen), hp.bottleneck_width)
     dnoise = None
-    if randomized and hp.density_noise > 0:                                                  # models.py:462-464, as `_forward`
-      if 'density_noise' in nz:
-        dnoise = nz['density_noise'].to(dev).float()
-        dnoise = dnoise.reshape(1, 1).expand(M0, 1) if dnoise.numel() == 1 else dnoise.reshape(M0, 1)
-      elif gen is not None:
-        dnoise = (torch.randn((1, 1), generator=gen, device=dev, dtype=f32).expand(M0, 1) if plan.tangent
-                  else torch.randn((M0, 1), generator=gen, device=dev, dtype=f32))
-      if dnoise is not None:
-        dnoise = rows(dnoise, 1)
+    if randomized and hp.density_noise > 0 and ('density_noise' in nz or gen is not None):
+      dnoise = rows(self._density_noise(plan, M0, 1, nz.get('density_noise'), gen), 1)
 
     tag = ('mlpcall', plan.module_name)
     g_means, g_covs = rows(means, 3), rows(covs, 9)
@@ -1507,32 +1594,21 @@ class Model:
       T_feat = self._buf((tag, 'T_feat'), (3 * Mp, plan.ldF), bf16)
       ops.ipe_from_gaussians_tangent(g_means, g_covs, plan.basis_dev, out=T_feat, **ipe_kw)
 
-    R = types.SimpleNamespace(viewdirs=vd, radii=None, origins=None, directions=None, glo_table=glo_tab)
-    missing = object()
-    keep_cam = getattr(self, '_glo_cam', missing)
-    try:
-      if glo_tab is not None:
-        self._glo_cam = self._const(('mlpcall', 'glo_idx'), (Mp,), lambda: torch.arange(Mp, dtype=torch.int32, device=dev))
-      if grouped:
-        out = self._chain_forward_grouped(plan, route, flat, feat, Mp, tag)
-      else:
-        out = self._mlp_forward(plan, route, flat, feat, Mp, 1, R, tag, False, bnoise=bnoise, T_feat=T_feat)
-    finally:
-      if keep_cam is missing:
-        self.__dict__.pop('_glo_cam', None)
-      else:
-        self._glo_cam = keep_cam
+    R = types.SimpleNamespace(viewdirs=vd, radii=None, origins=None, directions=None)
+    if grouped:
+      out = self._chain_forward_grouped(plan, route, flat, feat, Mp, tag)
+    else:
+      # (the caller's glo_vec as a table of its own, one row per sample)
+      glo_idx = None if glo_tab is None else self._const(('mlpcall', 'glo_idx'), (Mp,),
+                                                         lambda: torch.arange(Mp, dtype=torch.int32, device=dev))
+      out = self._mlp_forward(plan, route, flat, feat, Mp, 1, R, tag, False, bnoise=bnoise, T_feat=T_feat, glo_table=glo_tab,
+                              glo_cam=glo_idx)
 
     # density = act(raw + noise + bias), colour = act(premultiplier * raw + bias) padded (models.py:506,584-602): per sample
     # inside mnr_composite_fwd, the kernel the level loop takes both from; its step function here is a dummy (32 samples per row
     # of [0, 1]; weights and the composited colour are not used).
     nc = 32
-    ccfg = ops.composite_cfg(nc, opaque_background=False, density_act=hp.density_activation, density_bias=hp.density_bias,
-                             density_noise_std=hp.density_noise if dnoise is not None else 0.0, has_rgb=plan.has_rgb,
-                             rgb_act='identity' if plan.diffuse_on else hp.rgb_activation,
-                             rgb_premultiplier=1.0 if plan.diffuse_on else hp.rgb_premultiplier,
-                             rgb_bias=0.0 if plan.diffuse_on else hp.rgb_bias,
-                             rgb_padding=0.0 if plan.diffuse_on else hp.rgb_padding, bg_mode=0, bg_value=0.0)
+    ccfg = self._composite_cfg(plan, nc, dnoise is not None, False, 0, 0.0)
     t_dummy = self._const(('mlpcall', 'tdist'), (Mp, nc),
                           lambda: torch.linspace(0., 1., nc + 1, dtype=f32).to(dev).repeat(Mp // nc, 1).contiguous())
     d_dummy = self._const(('mlpcall', 'dirs'), (Mp, nc), lambda: torch.ones((Mp // nc, 3), dtype=f32, device=dev))
@@ -1626,268 +1702,244 @@ class Model:
     the list g_feat_out the bf16 [M, ldF] matrices whose sum is d loss / d features (one per trunk layer that reads the
     features: layer 0 and the skip layer); the list g_tfeat_out the [3 M, ldF] matrices whose sum is d loss / d (tangent feature
     rows) of the density-gradient normals' forward-mode network (`_tangent_backward`)."""
-    plan: MLPPlan = lv['plan']
-    hp = plan.hp
-    M, n, tag = lv['M'], lv['n'], lv['tag']
-    R = self._saved['rays']
-    mlp = lv['mlp']
-    route: Route = mlp['route']
-    acts = mlp['acts']
-    x_last = acts[-1]
-    W = plan.W
+    b = _LevelBwd(self, lv, flat, grads, g_feat_out)
+    plan, mlp, route, M, feat = b.plan, b.mlp, b.route, b.M, lv['feat']
     D = len(plan.trunk)
-    # Workspace of this pass, keyed by the stream it runs on: the proposal levels' backward runs on a side stream next to the
-    # NeRF level's (train_utils.create_train_step), and a proposal MLP that takes this per-layer path (not chain-eligible:
-    # non-ReLU activation, odd widths, MNR_FUSED_CHAIN=0) with the NeRF MLP's width and row count would otherwise share dA / dB /
-    # dV / dHB / ... with it.  Levels that run one after the other on the same stream share their buffers.
-    slot = 'nerf' if lv['level'] == self.num_levels - 1 else 'prop'
-
-    def dy_buf(i):
-      """dY of trunk layer i's output: two ping-pong buffers shared by the levels of a stream."""
-      return self._buf(('bwd', slot, 'dA' if (D - 1 - i) % 2 == 0 else 'dB', W), (M, W), bf16)
-
-    def dv_buf(i, nv):
-      return self._buf(('bwd', slot, 'dV0' if (nv - 1 - i) % 2 == 0 else 'dV1', WV), (M, WV), bf16)
-
-    if not route.chain:
-      dA = dy_buf(D - 1)
-
-    def gslice(off, size):
-      return grads[off:off + size]
-
-    relu = hp.net_activation == 'relu'
-    panel = route.panel                                   # the trunk's activations / masks / gradients are in panel storage
-    PAN = ops.LAYOUT_PANEL
-    lay_c = dict(c_layout=PAN) if panel else {}
-    lay_ac = dict(a1_layout=PAN, c_layout=PAN) if panel else {}
-    tn_a = dict(a_layout=PAN) if panel else {}
-
-    def act_vjp(z, d):
-      """Non-ReLU activations: d (gradient w.r.t. a layer's activation, just written without a mask) *= act'(z)."""
-      if not relu:
-        ops.act_bwd(hp.net_activation, z, d)
-
-    def mask_kw(i):
-      """ReLU VJP of trunk layer i's output: 1-bit mask if available, else the saved activation."""
-      if not relu:
-        return {}
-      if mlp['bits'][i] is not None:
-        return dict(bits_in=mlp['bits'][i])
-      return dict(mask=acts[i], ldmask=W)
-
-    def feat_grad(i, dy, dy_panel=False):
-      """d loss / d features through trunk layer i (0 or a skip layer): dY_i @ kernel_i[feature rows]^T -> bf16 [M, ldF]."""
-      if g_feat_out is None:
-        return
-      e_ = plan.packed[('trunk', i)]
-      out = self._buf(('bwd', slot, 'g_feat', len(g_feat_out)), (M, plan.ldF), bf16)
-      ops.gemm_nt(dy, self._w(plan, e_['bf_off'], plan.ldF, e_['bf_ld']), M=M, N=plan.ldF, K1=e_['bf_ld'], Cb=out,
-                  ldcb=plan.ldF, nb=plan.ldF, **(dict(a1_layout=PAN) if dy_panel else {}))
-      g_feat_out.append(out)
-
+    dA = None if route.chain else b.dy_buf(D - 1)        # the last trunk layer's dY: what every head VJP leaves behind
+    # 1. compositing VJP and head VJP, by the head's kind; 2. between the two for the merged head, its colour branch
     g_raw_grad = None
-    if plan.has_rgb and not plan.use_viewdirs:
-      g_raw_density, g_rgb = ops.composite_bwd(
-          lv['ccfg'], lv['raw_density'], lv['tdist'], R.directions, lv['weights'], raw_rgb=lv['raw_rgb'],
-          density_noise=lv['dnoise'], bg=lv['bg'], g_rgb_out=g_rgb_out, g_weights=g_weights, want_f32=True,
-          exposure_scale=lv['expo'], g_exposure_scale=g_expo if lv['expo'] is not None else None, losses=losses,
-          g_x_out=g_x_out)
-      # the 4-column head [density | rgb]: dX into the trunk, dW / db scattered to the two Dense layers
-      g4 = self._buf(('bwd', slot, 'g4'), (M, 4), f32)
-      g4[:, 0].copy_(g_raw_density.view(M))
-      g4[:, 1:4].copy_(g_rgb.view(M, 3))
-      dn, dr = plan.density, plan.rgb
-      w4 = self._buf(('bwd', slot, 'w4', W), (W, 4), f32)
-      w4[:, 0].copy_(flat[dn.kernel_off:dn.kernel_off + W])
-      w4[:, 1:4].copy_(flat[dr.kernel_off:dr.kernel_off + 3 * W].view(W, 3))
-      t4 = self._buf(('bwd', slot, 't4', W), (W + 1, 4), f32)
-      t4.zero_()
-      ops.small_head_bwd(x_last, W, g4, w4, M=M, K=W, Cn=4, dX=dA, lddx=W, relu_mask=relu, dW=t4[:W].view(-1), db=t4[W])
-      act_vjp(mlp['zs'][-1] if not relu else None, dA)
-      for (d, c0) in plan.head_segs:
-        ops.scatter_add(t4, 4, 0, c0, W, d.fan_out, gslice(d.kernel_off, W * d.fan_out), d.fan_out)
-        ops.scatter_add(t4, 4, W, c0, 1, d.fan_out, gslice(d.bias_off, d.fan_out), d.fan_out)
-    elif plan.has_rgb:
-      bw = hp.bottleneck_width
-      e = plan.packed['head']
-      nh = e['nb_pad']
-      # (columns beyond head_cols, and those of Ref-NeRF heads this MLP does not have, stay zero: keyed by module)
-      dHB = self._buf(('bwd', slot, 'dHB', nh, plan.module_name), (M, nh), bf16, zero=True)
-      # (the plain merged head [bottleneck | density] of 360.gin: the density column's weight gradient rides in the bottleneck's
-      # dW GEMM as a vector, below; it then also leaves the compositing VJP as the fp32 vector that GEMM reads)
-      # (for trunks of at least 512 columns: at 256 the merged N = 384 GEMM is six small tiles and the extra column buys nothing,
-      # blender_256 1.764 / 1.767 M rays/s merged against 1.749 / 1.764 M, llff_raw 546.0 against 545.9 k)
-      head_gcol = route.gcol
-      assert head_gcol or not panel
-      g_den_f32, g_rgb = ops.composite_bwd(
-          lv['ccfg'], lv['raw_density'], lv['tdist'], R.directions, lv['weights'], raw_rgb=lv['raw_rgb'],
-          density_noise=lv['dnoise'], bg=lv['bg'], g_rgb_out=g_rgb_out, g_weights=g_weights,
-          g_den_bf16=dHB.view(-1)[bw:], ld_bf16=nh, want_f32=head_gcol, exposure_scale=lv['expo'],
-          g_exposure_scale=g_expo if lv['expo'] is not None else None, losses=losses, g_x_out=g_x_out)
-      g_raw_rgb = g_rgb.view(M, 3)
-      if head_gcol:
-        # the density column of dHB once more as a contiguous bf16 vector, and the density bias gradient from the strided column
-        # (33 MB of 64-byte sectors): two small launches, issued HERE, before the proposal levels' persistent kernels fill
-        # the CUs from the side stream (behind them a 25-us launch of 512 small workgroups took 0.3-0.6 ms to get its CUs,
-        # with the main stream's next GEMM waiting for it: profiles/r3s3_step_seq_default.md)
-        g_vec = self._buf(('bwd', slot, 'g_den_vec'), (M,), bf16)
-        ops.cast_f32_to_bf16(g_den_f32.view(-1), 1, M, 1, g_vec, 1, 0)
-        ops.colsum(dHB.view(-1)[bw:], M, 1, gslice(plan.density.bias_off, 1), ld=nh)
-      if plan.diffuse_on:
-        # colour combine VJP: -> d raw specular rgb, and the diffuse / tint columns of the head gradient
-        g_raw_rgb = ops.ref_color_bwd(mlp['raw_rgb_pre'], mlp['small'], hp.rgb_premultiplier, hp.rgb_bias,
-                                      hp.rgb_padding, hp.use_specular_tint, g_raw_rgb.contiguous(), dHB, bw + 4, bw + 7)
-      # rgb Dense(3): dH, dW, db
-      WV = hp.net_width_viewdirs
-      vacts = mlp['vacts']
-      d = plan.rgb
-      NV = len(plan.view)
-      dV0 = dv_buf(NV - 1, NV)
-      h_last = vacts[-1]
-      ops.small_head_bwd(h_last, WV, g_raw_rgb, flat[d.kernel_off:d.kernel_off + d.fan_in * 3].view(d.fan_in, 3),
-                         M=M, K=WV, Cn=3, dX=dV0, lddx=WV, relu_mask=relu,
-                         dW=gslice(d.kernel_off, d.fan_in * 3), db=gslice(d.bias_off, 3))
-      act_vjp(mlp['vzs'][-1] if not relu else None, dV0)
-      dy = dV0
-      VI = mlp['VI']
-      dVIa = dVIb = None
-      want_glo = plan.glo > 0 and self._glo_cam is not None
-      gGa = self._buf(('bwd', slot, 'gGa'), (M, plan.glo), f32) if want_glo else None
-      gGb = None
-      glo_kw = lambda t: dict(Cf=t, ldcf=plan.glo, f0=plan.glo_col, nf=plan.glo) if want_glo else {}
-      for i in reversed(range(len(plan.view))):
-        d, concat = plan.view[i]
-        e = plan.packed[('view', i)]
-        inp = VI if i == 0 else vacts[i - 1]
-        in_w = plan.ldVI if i == 0 else WV
-        # dW (rows of the first input segment; then the skip-concat rows), db
-        ops.gemm_tn(inp, dy, gslice(d.kernel_off, d.fan_in * d.fan_out), M=M, K=in_w, N=WV,
-                    lda=inp.stride(0), ldb=WV, ldc=d.fan_out,
-                    k_valid=(plan.vi_width if i == 0 else WV), n_valid=d.fan_out,
-                    bias_out=gslice(d.bias_off, d.fan_out), bias_n_valid=d.fan_out)
-        if concat:
-          ops.gemm_tn(VI, dy, gslice(d.kernel_off + WV * d.fan_out, plan.vi_width * d.fan_out), M=M,
-                      K=plan.ldVI, N=WV, lda=plan.ldVI, ldb=WV, ldc=d.fan_out, k_valid=plan.vi_width,
-                      n_valid=d.fan_out)
-        if concat:
-          # the view input also receives gradient through the skip concat (bottleneck, IDE / n.v / GLO columns)
-          first_skip = dVIb is None
-          tVI = self._buf(('bwd', slot, 'dVIb', 0 if first_skip else 1), (M, plan.ldVI), bf16)
-          tG = self._buf(('bwd', slot, 'gGb', 0 if first_skip else 1), (M, plan.glo), f32) if want_glo else None
-          B2 = self._w(plan, e['b2_off'], plan.ldVI, e['b_ld'])
-          ops.gemm_nt(dy, B2, M=M, N=plan.ldVI, K1=e['b_ld'], Cb=tVI, ldcb=plan.ldVI, nb=plan.ldVI, **glo_kw(tG))
-          if first_skip:
-            dVIb, gGb = tVI, tG
-          else:                                    # more than one skip layer: sum the contributions
-            ops.add_cols_bf16(dVIb, tVI, dVIb, plan.ldVI)
-            if want_glo:
-              gGb.add_(tG)
-        Bw = self._w(plan, e['b_off'], e['b_rows'], e['b_ld'])
-        if i == 0:
-          if plan.ref:
-            dVIa = self._buf(('bwd', slot, 'dVIa'), (M, plan.ldVI), bf16)
-            ops.gemm_nt(dy, Bw, M=M, N=e['b_rows'], K1=e['b_ld'], Cb=dVIa, ldcb=plan.ldVI, nb=plan.ldVI, **glo_kw(gGa))
-          else:
-            ops.gemm_nt(dy, Bw, M=M, N=e['b_rows'], K1=e['b_ld'], Cb=dHB, ldcb=nh, nb=bw, **glo_kw(gGa))
-        else:
-          other = dv_buf(i - 1, NV)
-          if relu:
-            ops.gemm_nt(dy, Bw, M=M, N=WV, K1=e['b_ld'], mask=vacts[i - 1], ldmask=WV, Cb=other, ldcb=WV, nb=WV)
-          else:
-            ops.gemm_nt(dy, Bw, M=M, N=WV, K1=e['b_ld'], Cb=other, ldcb=WV, nb=WV)
-            act_vjp(mlp['vzs'][i - 1], other)
-          dy = other
-      if want_glo:
-        G = plan.glo
-        ops.glo_bwd(gGa, gGb, self._glo_cam, M // n, n, grads[self.glo_off:self.glo_off + self.num_glo_embeddings * G],
-                    self.num_glo_embeddings, G)
-      if dVIb is not None and not plan.ref:
-        # bottleneck gradient through the skip concat (a view MLP deeper than skip_layer_dir)
-        ops.add_cols_bf16(dHB, dVIb, dHB, bw)
-      if plan.dn and g_normals is not None:
-        g_raw_grad = ops.density_normals_bwd(mlp['raw_grad'], g_normals.view(M, 3))      # -> the tangent network, below
-      if plan.pn and g_npred is not None:
-        # VJP of normals_pred = -l2_normalize(grad_pred) into the grad_pred columns of the head gradient (zero without a loss on them)
-        ops.pred_normals_bwd(mlp['small'], 1, g_npred.view(M, 3), dHB, bw + 1)
-      if plan.ref:
-        # IDE / reflection / normalisation VJP: fills the bottleneck (dVIa + dVIb), grad_pred and roughness
-        # columns of dHB and returns the gradient w.r.t. d raw_density / d mean for the tangent network.
-        g_raw_grad = ops.ref_head_bwd(mlp['small'], mlp.get('raw_grad'), R.viewdirs, n, plan.ide, hp.roughness_bias,
-                                      dVIa, dVIb, bw, g_npred, g_normals, dHB, bw + 1, bw + 10, features=plan.features,
-                                      deg_view=hp.deg_view)
-      # merged head: dW, db, dX_last
-      if head_gcol:
-        # dW_bottleneck += x^T dHB[:, :bw] straight into the flat gradient (256x256 tiles), dw_density += x^T g as one more
-        # column of the same launch (db_density: above)
-        db_, dd_ = plan.bottleneck, plan.density
-        ops.gemm_tn(x_last, dHB, gslice(db_.kernel_off, W * bw), M=M, K=W, N=bw, lda=W, ldb=nh, ldc=bw,
-                    bias_out=gslice(db_.bias_off, bw), bias_n_valid=bw, gcol=g_vec, gcol_out=gslice(dd_.kernel_off, W), **tn_a)
-      else:
-        tmpW = self._buf(('bwd', slot, 'tmpW', W, nh), (W, nh), f32)
-        tmpW.zero_()
-        tmpb = self._buf(('bwd', slot, 'tmpb', nh), (nh,), f32)
-        tmpb.zero_()
-        ops.gemm_tn(x_last, dHB, tmpW, M=M, K=W, N=nh, lda=W, ldb=nh, ldc=nh, bias_out=tmpb,
-                    bias_n_valid=plan.head_cols)
-        for (d, c0) in plan.head_segs:
-          ops.scatter_add(tmpW, nh, 0, c0, W, d.fan_out, gslice(d.kernel_off, W * d.fan_out), d.fan_out)
-          ops.scatter_add(tmpb, nh, 0, c0, 1, d.fan_out, gslice(d.bias_off, d.fan_out), d.fan_out)
-      # (K = the head's columns rounded to the GEMM's 64-column K granule, not to the buffers' 128: 320 instead of 384 at 360.gin)
-      ops.gemm_nt(dHB, self._bw(plan, 'head'), M=M, N=_rup(W, 128), K1=_rup(plan.head_cols, 32 if (panel and _HEAD_K32) else 64),
-                  Cb=dA, ldcb=W, nb=W, **mask_kw(len(acts) - 1), **lay_c)
-      act_vjp(mlp['zs'][-1] if not relu else None, dA)
+    if not plan.has_rgb:
+      g_raw_density, _ = self._composite_vjp(lv, g_rgb_out, g_weights, None, losses, g_x_out)
+      self._density_head_bwd(b, g_raw_density, dA)
+    elif not plan.use_viewdirs:
+      g_raw_density, g_rgb = self._composite_vjp(lv, g_rgb_out, g_weights, g_expo, losses, g_x_out)
+      self._head4_bwd(b, g_raw_density, g_rgb, dA)
     else:
-      g_raw_density, _ = ops.composite_bwd(
-          lv['ccfg'], lv['raw_density'], lv['tdist'], R.directions, lv['weights'], density_noise=lv['dnoise'],
-          bg=lv['bg'], g_rgb_out=g_rgb_out, g_weights=g_weights, want_f32=True, losses=losses, g_x_out=g_x_out)
-      d = plan.density
-      if route.chain:
-        # fused dX chain: head dW / db from the last activation, then every dY_i in one launch; dW_i = x_{i-1}^T dY_i below
-        w_head = flat[d.kernel_off:d.kernel_off + W]
-        ops.small_head_bwd(x_last, W, g_raw_density.view(M, 1), w_head.view(W, 1), M=M, K=W, Cn=1, dX=None,
-                           relu_mask=False, dW=gslice(d.kernel_off, W), db=gslice(d.bias_off, 1))
-        # (keyed by level: the proposal levels' backward passes may run side by side on streams of their own)
-        # (the last dY = mask * (g (x) w_head) is not stored when its only reader, the last layer's weight-gradient GEMM, can
-        # build it from the factors: `_rank1_last`)
-        r1 = self._rank1_last(plan, g_feat_out is not None)
-        dYs = [None if (r1 and i == D - 1) else self._buf(('bwd', slot, 'dYc', W, i, lv['level']), (M, W), bf16) for i in range(D)]
-        ops.mlp_chain_bwd(g_raw_density.view(M), w_head, mlp['bits'], self._chain_bws(plan), dYs, M=M, W=W)
-        feat = lv['feat']
-        for i, (_, concat) in enumerate(plan.trunk):
-          self._trunk_dw(plan, grads, i, acts, feat, dYs[i], M,
-                         rank1=(g_raw_density.view(M), w_head, mlp['bits'][i]) if dYs[i] is None else None)
-          if i == 0 or concat:
-            feat_grad(i, dYs[i])
-        return
-      ops.small_head_bwd(x_last, W, g_raw_density.view(M, 1), flat[d.kernel_off:d.kernel_off + W].view(W, 1),
-                         M=M, K=W, Cn=1, dX=dA, lddx=W, relu_mask=relu,
-                         dW=gslice(d.kernel_off, W), db=gslice(d.bias_off, 1))
-      act_vjp(mlp['zs'][-1] if not relu else None, dA)
-    feat = lv['feat']
+      dHB, g_vec, g_raw_rgb = self._merged_head_composite_vjp(b, g_rgb_out, g_weights, g_expo, losses, g_x_out)
+      dVI = self._color_bwd(b, g_raw_rgb, dHB)
+      g_raw_grad = self._merged_head_bwd(b, dHB, g_vec, dVI, g_normals, g_npred, dA)
+    # 3. the tangent network of the density-gradient normals
     t_extras = None
     if g_raw_grad is not None:
-      t_extras = self._tangent_backward(plan, flat, grads, mlp, feat, M, g_raw_grad, slot, g_tfeat_out)
-    if route.chain_trunk:
-      # fused dX chain from the dY_last the head GEMMs left in dA; then dW_i = [x_{i-1} | feat]^T dY_i per layer
-      dYs = [self._buf(('bwd', slot, 'dYc', W, i), (M, W), bf16) for i in range(D - 1)] + [None]
-      ops.mlp_chain_bwd(None, None, mlp['bits'], self._chain_bws(plan), dYs, M=M, W=W, dY_in=dA)
-      dYs[D - 1] = dA
-      for i, (_, concat) in enumerate(plan.trunk):
-        self._trunk_dw(plan, grads, i, acts, feat, dYs[i], M)
-        if i == 0 or concat:
-          feat_grad(i, dYs[i])
-      return
-    # trunk: per layer its dW (independent of the dX chain: on the dW stream when that switch is on), then the dX GEMM the
-    # next layer waits for
-    dy = dA
-    pair = bool(_PAIR_DXDW and panel and self.device.type == 'cuda' and (M // 256) % 8 == 0)
-    if pair:
-      cur_s = torch.cuda.current_stream(self.device)
-      if getattr(self, '_dw_stream', None) is None:
-        self._dw_stream = torch.cuda.Stream(device=self.device)
-        self._half_cus = max(8, torch.cuda.get_device_properties(self.device).multi_processor_count // 2 // 8 * 8)
-        self._pair_events = {}
-      dw_done = None
+      t_extras = self._tangent_backward(plan, flat, grads, mlp, feat, M, g_raw_grad, b.slot, g_tfeat_out)
+    # 4. the trunk, by route
+    if route.chain:
+      # (dYc keyed by level: the proposal levels' backward passes may run side by side on streams of their own)
+      d = plan.density
+      self._chain_trunk_bwd(plan, grads, mlp['acts'], mlp['bits'], feat, M, ('bwd', b.slot), (lv['level'],),
+                            head=(g_raw_density.view(M), flat[d.kernel_off:d.kernel_off + plan.W]),
+                            feat_grad=b.feat_grad if g_feat_out is not None else None)
+    elif route.chain_trunk:
+      self._chain_trunk_bwd(plan, grads, mlp['acts'], mlp['bits'], feat, M, ('bwd', b.slot), (), dY_in=dA, feat_grad=b.feat_grad)
+    else:
+      self._trunk_bwd(b, dA, feat, t_extras)
+
+  def _composite_vjp(self, lv, g_rgb_out, g_weights, g_expo, losses, g_x_out=None, **kw):
+    """The compositing VJP of the saved level `lv`, its losses evaluated and differentiated inside the launch (ops.composite_bwd)
+    -> (g_raw_density, g_raw_rgb).  A level without a colour has neither raw_rgb nor an exposure scale.  `kw`: what the head's
+    kind asks for (want_f32, g_den_bf16 / ld_bf16, g_raw_density_out)."""
+    expo = lv['expo'] if lv['plan'].has_rgb else None
+    return ops.composite_bwd(lv['ccfg'], lv['raw_density'], lv['tdist'], self._saved['rays'].directions, lv['weights'],
+                             raw_rgb=lv['raw_rgb'], density_noise=lv['dnoise'], bg=lv['bg'], g_rgb_out=g_rgb_out, g_weights=g_weights,
+                             exposure_scale=expo, g_exposure_scale=g_expo if expo is not None else None, losses=losses,
+                             g_x_out=g_x_out, **kw)
+
+  def _density_head_bwd(self, b: _LevelBwd, g_raw_density, dA):
+    """VJP of a density-only MLP's Dense(1) head: dW / db from the last activation, and the last trunk layer's dY into dA; dA
+    None (the fused chain): dW / db only, `_chain_trunk_bwd` builds every dY from (g, w_head) itself."""
+    plan, M, W, d = b.plan, b.M, b.plan.W, b.plan.density
+    ops.small_head_bwd(b.mlp['acts'][-1], W, g_raw_density.view(M, 1), b.flat[d.kernel_off:d.kernel_off + W].view(W, 1), M=M, K=W, Cn=1,
+                       dX=dA, lddx=0 if dA is None else W, relu_mask=b.relu and dA is not None,
+                       dW=b.gslice(d.kernel_off, W), db=b.gslice(d.bias_off, 1))
+    if dA is not None:
+      b.act_vjp(b.mlp['zs'][-1] if not b.relu else None, dA)
+
+  def _head4_bwd(self, b: _LevelBwd, g_raw_density, g_rgb, dA):
+    """VJP of the 4-column head [density | rgb] (use_viewdirs = False): dX into dA, dW / db scattered to the two Dense layers."""
+    plan, M, W, flat = b.plan, b.M, b.plan.W, b.flat
+    g4 = self._buf(('bwd', b.slot, 'g4'), (M, 4), f32)
+    g4[:, 0].copy_(g_raw_density.view(M))
+    g4[:, 1:4].copy_(g_rgb.view(M, 3))
+    dn, dr = plan.density, plan.rgb
+    w4 = self._buf(('bwd', b.slot, 'w4', W), (W, 4), f32)
+    w4[:, 0].copy_(flat[dn.kernel_off:dn.kernel_off + W])
+    w4[:, 1:4].copy_(flat[dr.kernel_off:dr.kernel_off + 3 * W].view(W, 3))
+    t4 = self._buf(('bwd', b.slot, 't4', W), (W + 1, 4), f32)
+    t4.zero_()
+    ops.small_head_bwd(b.mlp['acts'][-1], W, g4, w4, M=M, K=W, Cn=4, dX=dA, lddx=W, relu_mask=b.relu, dW=t4[:W].view(-1), db=t4[W])
+    b.act_vjp(b.mlp['zs'][-1] if not b.relu else None, dA)
+    for (d, c0) in plan.head_segs:
+      ops.scatter_add(t4, 4, 0, c0, W, d.fan_out, b.gslice(d.kernel_off, W * d.fan_out), d.fan_out)
+      ops.scatter_add(t4, 4, W, c0, 1, d.fan_out, b.gslice(d.bias_off, d.fan_out), d.fan_out)
+
+  def _merged_head_composite_vjp(self, b: _LevelBwd, g_rgb_out, g_weights, g_expo, losses, g_x_out):
+    """The compositing VJP under the merged head [bottleneck | density | Ref-NeRF columns]: the density gradient goes straight
+    into its column of the head gradient dHB [M, nh] bf16 -> (dHB, g_vec, g_raw_rgb [M, 3]); g_vec: with `route.gcol` that
+    column once more as a contiguous vector, for the head's weight-gradient GEMM (`_merged_head_bwd`)."""
+    plan, M, route = b.plan, b.M, b.route
+    bw, nh = plan.hp.bottleneck_width, plan.packed['head']['nb_pad']
+    # (columns beyond head_cols, and those of Ref-NeRF heads this MLP does not have, stay zero: keyed by module)
+    dHB = self._buf(('bwd', b.slot, 'dHB', nh, plan.module_name), (M, nh), bf16, zero=True)
+    # (the plain merged head [bottleneck | density] of 360.gin: the density column's weight gradient rides in the bottleneck's
+    # dW GEMM as a vector; it then also leaves the compositing VJP as the fp32 vector that GEMM reads)
+    # (for trunks of at least 512 columns: at 256 the merged N = 384 GEMM is six small tiles and the extra column buys nothing,
+    # blender_256 1.764 / 1.767 M rays/s merged against 1.749 / 1.764 M, llff_raw 546.0 against 545.9 k)
+    assert route.gcol or not route.panel
+    g_den_f32, g_rgb = self._composite_vjp(b.lv, g_rgb_out, g_weights, g_expo, losses, g_x_out, g_den_bf16=dHB.view(-1)[bw:],
+                                           ld_bf16=nh, want_f32=route.gcol)
+    g_vec = None
+    if route.gcol:
+      # the density column of dHB once more as a contiguous bf16 vector, and the density bias gradient from the strided column
+      # (33 MB of 64-byte sectors): two small launches, issued HERE, before the proposal levels' persistent kernels fill
+      # the CUs from the side stream (behind them a 25-us launch of 512 small workgroups took 0.3-0.6 ms to get its CUs,
+      # with the main stream's next GEMM waiting for it: profiles/r3s3_step_seq_default.md)
+      g_vec = self._buf(('bwd', b.slot, 'g_den_vec'), (M,), bf16)
+      ops.cast_f32_to_bf16(g_den_f32.view(-1), 1, M, 1, g_vec, 1, 0)
+      ops.colsum(dHB.view(-1)[bw:], M, 1, b.gslice(plan.density.bias_off, 1), ld=nh)
+    return dHB, g_vec, g_rgb.view(M, 3)
+
+  def _color_bwd(self, b: _LevelBwd, g_raw_rgb, dHB):
+    """VJP of the colour branch (`_color_forward`): the colour combine of a diffuse colour, the rgb Dense(3), the view MLP with its
+    skip concats, the GLO vectors.
+    In: g_raw_rgb [M, 3] fp32, d loss / d raw_rgb as the compositing VJP left it; of the forward result b.mlp its 'VI', 'vacts',
+    'vzs' and, with a diffuse colour, 'raw_rgb_pre' and 'small'.
+    Out: the view and rgb layers' dW / db and the GLO table's gradient, accumulated into b.grads; with a diffuse colour the
+    diffuse / tint columns of dHB; and the view input's gradient: under the plain head its bottleneck columns written into
+    dHB[:, :bw] (nothing else of it is needed) and (None, None) returned, under the Ref-NeRF head -> (dVIa, dVIb), bf16 [M, ldVI]
+    through view layer 0 and through the skip concats (None without one), whose sum `ref_head_bwd` takes."""
+    plan, mlp, flat, M, n, relu, gslice = b.plan, b.mlp, b.flat, b.M, b.n, b.relu, b.gslice
+    hp, bw, nh, slot = plan.hp, plan.hp.bottleneck_width, dHB.shape[1], b.slot
+    if plan.diffuse_on:
+      # colour combine VJP: -> d raw specular rgb, and the diffuse / tint columns of the head gradient
+      g_raw_rgb = ops.ref_color_bwd(mlp['raw_rgb_pre'], mlp['small'], hp.rgb_premultiplier, hp.rgb_bias, hp.rgb_padding,
+                                    hp.use_specular_tint, g_raw_rgb.contiguous(), dHB, bw + 4, bw + 7)
+    # rgb Dense(3): dH, dW, db
+    WV, NV, VI, vacts, d = hp.net_width_viewdirs, len(plan.view), mlp['VI'], mlp['vacts'], plan.rgb
+    dy = b.dv_buf(NV - 1, NV)
+    ops.small_head_bwd(vacts[-1], WV, g_raw_rgb, flat[d.kernel_off:d.kernel_off + d.fan_in * 3].view(d.fan_in, 3), M=M, K=WV, Cn=3,
+                       dX=dy, lddx=WV, relu_mask=relu, dW=gslice(d.kernel_off, d.fan_in * 3), db=gslice(d.bias_off, 3))
+    b.act_vjp(mlp['vzs'][-1] if not relu else None, dy)
+    dVIa = dVIb = None
+    want_glo = plan.glo > 0 and self._glo_cam is not None
+    gGa = self._buf(('bwd', slot, 'gGa'), (M, plan.glo), f32) if want_glo else None
+    gGb = None
+    glo_kw = lambda t: dict(Cf=t, ldcf=plan.glo, f0=plan.glo_col, nf=plan.glo) if want_glo else {}
+    for i in reversed(range(len(plan.view))):
+      d, concat = plan.view[i]
+      e = plan.packed[('view', i)]
+      inp = VI if i == 0 else vacts[i - 1]
+      in_w = plan.ldVI if i == 0 else WV
+      # dW (rows of the first input segment; then the skip-concat rows), db
+      ops.gemm_tn(inp, dy, gslice(d.kernel_off, d.fan_in * d.fan_out), M=M, K=in_w, N=WV, lda=inp.stride(0), ldb=WV, ldc=d.fan_out,
+                  k_valid=(plan.vi_width if i == 0 else WV), n_valid=d.fan_out, bias_out=gslice(d.bias_off, d.fan_out),
+                  bias_n_valid=d.fan_out)
+      if concat:
+        ops.gemm_tn(VI, dy, gslice(d.kernel_off + WV * d.fan_out, plan.vi_width * d.fan_out), M=M, K=plan.ldVI, N=WV, lda=plan.ldVI,
+                    ldb=WV, ldc=d.fan_out, k_valid=plan.vi_width, n_valid=d.fan_out)
+        # the view input also receives gradient through the skip concat (bottleneck, IDE / n.v / GLO columns)
+        first_skip = dVIb is None
+        tVI = self._buf(('bwd', slot, 'dVIb', 0 if first_skip else 1), (M, plan.ldVI), bf16)
+        tG = self._buf(('bwd', slot, 'gGb', 0 if first_skip else 1), (M, plan.glo), f32) if want_glo else None
+        B2 = self._w(plan, e['b2_off'], plan.ldVI, e['b_ld'])
+        ops.gemm_nt(dy, B2, M=M, N=plan.ldVI, K1=e['b_ld'], Cb=tVI, ldcb=plan.ldVI, nb=plan.ldVI, **glo_kw(tG))
+        if first_skip:
+          dVIb, gGb = tVI, tG
+        else:                                    # more than one skip layer: sum the contributions
+          ops.add_cols_bf16(dVIb, tVI, dVIb, plan.ldVI)
+          if want_glo:
+            gGb.add_(tG)
+      Bw = self._w(plan, e['b_off'], e['b_rows'], e['b_ld'])
+      if i == 0:
+        if plan.ref:
+          dVIa = self._buf(('bwd', slot, 'dVIa'), (M, plan.ldVI), bf16)
+          ops.gemm_nt(dy, Bw, M=M, N=e['b_rows'], K1=e['b_ld'], Cb=dVIa, ldcb=plan.ldVI, nb=plan.ldVI, **glo_kw(gGa))
+        else:
+          ops.gemm_nt(dy, Bw, M=M, N=e['b_rows'], K1=e['b_ld'], Cb=dHB, ldcb=nh, nb=bw, **glo_kw(gGa))
+      else:
+        other = b.dv_buf(i - 1, NV)
+        if relu:
+          ops.gemm_nt(dy, Bw, M=M, N=WV, K1=e['b_ld'], mask=vacts[i - 1], ldmask=WV, Cb=other, ldcb=WV, nb=WV)
+        else:
+          ops.gemm_nt(dy, Bw, M=M, N=WV, K1=e['b_ld'], Cb=other, ldcb=WV, nb=WV)
+          b.act_vjp(mlp['vzs'][i - 1], other)
+        dy = other
+    if want_glo:
+      ops.glo_bwd(gGa, gGb, self._glo_cam, M // n, n, gslice(self.glo_off, self.num_glo_embeddings * plan.glo), self.num_glo_embeddings,
+                  plan.glo)
+    if plan.ref:
+      return dVIa, dVIb
+    if dVIb is not None:
+      # bottleneck gradient through the skip concat (a view MLP deeper than skip_layer_dir)
+      ops.add_cols_bf16(dHB, dVIb, dHB, bw)
+    return None, None
+
+  def _merged_head_bwd(self, b: _LevelBwd, dHB, g_vec, dVI, g_normals, g_npred, dA):
+    """VJP of the merged head from its gradient dHB (density column: `_merged_head_composite_vjp`; bottleneck columns, or
+    dVI = (dVIa, dVIb) under the Ref-NeRF head: `_color_bwd`): the normal fields' and the Ref-NeRF head's VJPs into their columns
+    of dHB, the head's dW / db, and its dX, the last trunk layer's dY, into dA -> g_raw_grad [3, M], the gradient of the
+    density's gradient for `_tangent_backward`, or None."""
+    plan, mlp, M, W = b.plan, b.mlp, b.M, b.plan.W
+    hp, bw, nh, gslice = plan.hp, plan.hp.bottleneck_width, dHB.shape[1], b.gslice
+    x_last = mlp['acts'][-1]
+    g_raw_grad = None
+    if plan.dn and g_normals is not None:
+      g_raw_grad = ops.density_normals_bwd(mlp['raw_grad'], g_normals.view(M, 3))      # -> the tangent network
+    if plan.pn and g_npred is not None:
+      # VJP of normals_pred = -l2_normalize(grad_pred) into the grad_pred columns of the head gradient (zero without a loss on them)
+      ops.pred_normals_bwd(mlp['small'], 1, g_npred.view(M, 3), dHB, bw + 1)
+    if plan.ref:
+      # IDE / reflection / normalisation VJP: fills the bottleneck (dVIa + dVIb), grad_pred and roughness
+      # columns of dHB and returns the gradient w.r.t. d raw_density / d mean for the tangent network.
+      g_raw_grad = ops.ref_head_bwd(mlp['small'], mlp.get('raw_grad'), self._saved['rays'].viewdirs, b.n, plan.ide, hp.roughness_bias,
+                                    dVI[0], dVI[1], bw, g_npred, g_normals, dHB, bw + 1, bw + 10, features=plan.features,
+                                    deg_view=hp.deg_view)
+    if b.route.gcol:
+      # dW_bottleneck += x^T dHB[:, :bw] straight into the flat gradient (256x256 tiles), dw_density += x^T g as one more
+      # column of the same launch (db_density: `_merged_head_composite_vjp`)
+      db_, dd_ = plan.bottleneck, plan.density
+      ops.gemm_tn(x_last, dHB, gslice(db_.kernel_off, W * bw), M=M, K=W, N=bw, lda=W, ldb=nh, ldc=bw,
+                  bias_out=gslice(db_.bias_off, bw), bias_n_valid=bw, gcol=g_vec, gcol_out=gslice(dd_.kernel_off, W), **b.tn_a)
+    else:
+      tmpW = self._buf(('bwd', b.slot, 'tmpW', W, nh), (W, nh), f32)
+      tmpW.zero_()
+      tmpb = self._buf(('bwd', b.slot, 'tmpb', nh), (nh,), f32)
+      tmpb.zero_()
+      ops.gemm_tn(x_last, dHB, tmpW, M=M, K=W, N=nh, lda=W, ldb=nh, ldc=nh, bias_out=tmpb, bias_n_valid=plan.head_cols)
+      for (d, c0) in plan.head_segs:
+        ops.scatter_add(tmpW, nh, 0, c0, W, d.fan_out, gslice(d.kernel_off, W * d.fan_out), d.fan_out)
+        ops.scatter_add(tmpb, nh, 0, c0, 1, d.fan_out, gslice(d.bias_off, d.fan_out), d.fan_out)
+    # (K = the head's columns rounded to the GEMM's 64-column K granule, not to the buffers' 128: 320 instead of 384 at 360.gin)
+    ops.gemm_nt(dHB, self._bw(plan, 'head'), M=M, N=_rup(W, 128), K1=_rup(plan.head_cols, 32 if (b.route.panel and _HEAD_K32) else 64),
+                Cb=dA, ldcb=W, nb=W, **b.mask_kw(len(mlp['acts']) - 1), **b.lay_c)
+    b.act_vjp(mlp['zs'][-1] if not b.relu else None, dA)
+    return g_raw_grad
+
+  def _chain_trunk_bwd(self, plan: MLPPlan, grads, acts, bits, feat, M, pre, post, head=None, dY_in=None, feat_grad=None):
+    """VJP of a trunk on the fused chain: every dY_i in ONE launch (mnr_mlp_chain_bwd), then per layer dW_i = [x_{i-1} | feat]^T
+    dY_i and, where `feat_grad` (a `_LevelBwd.feat_grad`) is given, the feature gradient of layer 0 and the skip layer.
+    The last dY is dY_in [M, W] (the heads' dX), or built from head = (g [M], w_head [W]) of a Dense(1) head (a density-only MLP);
+    it is then not stored when its only reader, the last layer's weight-gradient GEMM, can build it from the factors itself
+    (`_rank1_last`).  The other dY_i live in the buffers pre + ('dYc', W, i) + post."""
+    W, D = plan.W, len(plan.trunk)
+    g, w_head = head if dY_in is None else (None, None)
+    unstored = dY_in is not None or self._rank1_last(plan, feat_grad is not None)
+    dYs = [None if (unstored and i == D - 1) else self._buf(pre + ('dYc', W, i) + post, (M, W), bf16) for i in range(D)]
+    ops.mlp_chain_bwd(g, w_head, bits, self._chain_bws(plan), dYs, M=M, W=W, dY_in=dY_in)
+    if dY_in is not None:
+      dYs[D - 1] = dY_in
+    for i, (_, concat) in enumerate(plan.trunk):
+      self._trunk_dw(plan, grads, i, acts, feat, dYs[i], M, rank1=(g, w_head, bits[i]) if dYs[i] is None else None)
+      if feat_grad is not None and (i == 0 or concat):
+        feat_grad(i, dYs[i])
+
+  def _pair_streams(self):
+    """The paired dX / dW path's streams and events (`_PAIR_DXDW`) -> (the current stream, pair_event); the side stream, half the
+    chip's CU count and the event cache are made on first use."""
+    cur_s = torch.cuda.current_stream(self.device)
+    if getattr(self, '_dw_stream', None) is None:
+      self._dw_stream = torch.cuda.Stream(device=self.device)
+      self._half_cus = max(8, torch.cuda.get_device_properties(self.device).multi_processor_count // 2 // 8 * 8)
+      self._pair_events = {}
 
     def pair_event(kind, i):
       """One cached event per (kind, trunk layer): nothing is allocated per step."""
@@ -1896,6 +1948,17 @@ class Model:
         ev = self._pair_events[(kind, i)] = torch.cuda.Event()
       return ev
 
+    return cur_s, pair_event
+
+  def _trunk_bwd(self, b: _LevelBwd, dy, feat, t_extras):
+    """VJP of a per-layer trunk from its last layer's dY `dy`: per layer its dW (independent of the dX chain: on the dW stream
+    when `_PAIR_DXDW` applies), then the dX GEMM the next layer waits for.  t_extras: `_tangent_backward`'s act'' terms, or None."""
+    plan, mlp, grads, M, W, relu = b.plan, b.mlp, b.grads, b.M, b.plan.W, b.relu
+    acts, panel = mlp['acts'], b.route.panel
+    pair = bool(_PAIR_DXDW and panel and self.device.type == 'cuda' and (M // 256) % 8 == 0)
+    if pair:
+      cur_s, pair_event = self._pair_streams()
+      dw_done = None
     try:
       for i in reversed(range(len(plan.trunk))):
         concat = plan.trunk[i][1]
@@ -1911,11 +1974,11 @@ class Model:
             done = pair_event('done', i)
             done.record(self._dw_stream)
           if concat:
-            feat_grad(i, dy, dy_panel=panel)
+            b.feat_grad(i, dy, dy_panel=panel)
           if dw_done is not None:
             cur_s.wait_event(dw_done)                      # dX_i overwrites the buffer dW_{i+1} read its dY from
-          other = dy_buf(i - 1)
-          self._trunk_dx(plan, i, dy, other, M, max_wgs=self._half_cus, **mask_kw(i - 1), **lay_ac)
+          other = b.dy_buf(i - 1)
+          self._trunk_dx(plan, i, dy, other, M, max_wgs=self._half_cus, **b.mask_kw(i - 1), **b.lay_ac)
           dw_done = done
           dy = other
           continue
@@ -1924,11 +1987,11 @@ class Model:
           dw_done = None
         self._trunk_dw(plan, grads, i, acts, feat, dy, M, panel=panel)
         if i == 0 or concat:
-          feat_grad(i, dy, dy_panel=panel)
+          b.feat_grad(i, dy, dy_panel=panel)
         if i > 0:
-          other = dy_buf(i - 1)
-          self._trunk_dx(plan, i, dy, other, M, walk_descending=bool(i & 1), **mask_kw(i - 1), **lay_ac)
-          act_vjp(mlp['zs'][i - 1] if not relu else None, other)
+          other = b.dy_buf(i - 1)
+          self._trunk_dx(plan, i, dy, other, M, walk_descending=bool(i & 1), **b.mask_kw(i - 1), **b.lay_ac)
+          b.act_vjp(mlp['zs'][i - 1] if not relu else None, other)
           dy = other
     finally:
       # whatever path leaves the loop: the side stream's writes into `grads` (fp32 atomics of the last dW launch) are ordered
@@ -1946,13 +2009,11 @@ class Model:
     plan: MLPPlan = lvs[0]['plan']
     M, W, D = lvs[0]['M'], plan.W, len(plan.trunk)
     Mall = Lg * M
-    R = self._saved['rays']
     g_all = self._buf(('bwd', 'g_props', Lg), (Mall,), f32)
     for k, lv in enumerate(lvs):
       assert lv['group'] == (k, Lg) and lv['M'] == M and lv['plan'] is plan and lv['mlp']['route'].chain
-      ops.composite_bwd(lv['ccfg'], lv['raw_density'], lv['tdist'], R.directions, lv['weights'],
-                        density_noise=lv['dnoise'], bg=lv['bg'], g_rgb_out=None, g_weights=g_weights[k], want_f32=True,
-                        losses=losses[k], g_raw_density_out=g_all[k * M:(k + 1) * M].view(lv['raw_density'].shape))
+      self._composite_vjp(lv, None, g_weights[k], None, losses[k],
+                          g_raw_density_out=g_all[k * M:(k + 1) * M].view(lv['raw_density'].shape))
 
     def whole(name, cols, dtype):
       return self._buf((('lvl', 'props', Lg), name), (Mall,) + cols, dtype)
@@ -1964,11 +2025,7 @@ class Model:
     w_head = flat[d.kernel_off:d.kernel_off + W]
     ops.small_head_bwd(acts[-1], W, g_all.view(Mall, 1), w_head.view(W, 1), M=Mall, K=W, Cn=1, dX=None,
                        relu_mask=False, dW=grads[d.kernel_off:d.kernel_off + W], db=grads[d.bias_off:d.bias_off + 1])
-    r1 = self._rank1_last(plan, False)
-    dYs = [None if (r1 and i == D - 1) else self._buf(('bwd', 'dYc', W, i, 'props'), (Mall, W), bf16) for i in range(D)]
-    ops.mlp_chain_bwd(g_all, w_head, bits, self._chain_bws(plan), dYs, M=Mall, W=W)
-    for i in range(D):
-      self._trunk_dw(plan, grads, i, acts, feat, dYs[i], Mall, rank1=(g_all, w_head, bits[i]) if dYs[i] is None else None)
+    self._chain_trunk_bwd(plan, grads, acts, bits, feat, Mall, ('bwd',), ('props',), head=(g_all, w_head))
 
   def _tangent_backward(self, plan, flat, grads, mlp, feat, M, g_raw_grad, slot, g_tfeat_out=None):
     """Backward pass through the tangent network T_l = bits_l * (T_{l-1} W_l), raw_grad = T_last w_density
