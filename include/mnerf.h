@@ -680,6 +680,7 @@ int mnr_grad_sqnorm(const float* grad, int64_t begin, int64_t end, float max_val
 typedef struct {
   float lr, b1, b2, eps;
   float bias_corr1, bias_corr2;  /* 1 - b1^t, 1 - b2^t                          */
+  float one_minus_b1, one_minus_b2; /* float(1 - b) formed in double, as optax does: 1.0f - 0.999f is 0.00099998713f, not 0.001f */
   float grad_max_val;            /* 0: off                                      */
   float grad_max_norm;           /* 0: off                                      */
 } mnr_adam_cfg;

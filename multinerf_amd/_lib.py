@@ -220,8 +220,8 @@ class TsdfArgs(C.Structure):
 
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
-              ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('grad_max_val', C.c_float),
-              ('grad_max_norm', C.c_float)]
+              ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('one_minus_b1', C.c_float),
+              ('one_minus_b2', C.c_float), ('grad_max_val', C.c_float), ('grad_max_norm', C.c_float)]
 
 
 i64, i32, f32 = C.c_int64, C.c_int, C.c_float

@@ -866,8 +866,8 @@ extern "C" int mnr_act_fwd_bf16(int kind, int64_t n, const uint16_t* z, uint16_t
 //             which joins the PRIMAL backward pass's gradient of that layer (autodiff's second-order term of the "double backward").
 __device__ __forceinline__ float mnr_act_deriv2(int kind, float z) {
   const float sg = mnr_sigmoid(z);
-  const float d = sg * (1.0f - sg);
-  if (kind == 1) return d;                                         // softplus'' = sigmoid'
+  const float d = sg * mnr_sigmoid(-z);                            // sigmoid' = sg (1 - sg): 1 - sg as sigmoid(-z), which does not cancel for z >~ 10
+  if (kind == 1) return d;                                       // softplus'' = sigmoid'
   return d * (2.0f + z * (1.0f - 2.0f * sg));                      // silu'' = sigmoid' (2 + z (1 - 2 sigmoid))
 }
 

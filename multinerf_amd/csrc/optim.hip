@@ -88,8 +88,8 @@ __global__ void clip_adam_kernel(mnr_adam_cfg c, int64_t begin, int64_t end, con
     float g = grad[i];
     if (c.grad_max_val > 0.0f && g == g) g = fminf(fmaxf(g, -c.grad_max_val), c.grad_max_val);
     g = op_nan_to_num(mult * g);
-    const float m = c.b1 * mu[i] + (1.0f - c.b1) * g;
-    const float v = c.b2 * nu[i] + (1.0f - c.b2) * g * g;
+    const float m = c.b1 * mu[i] + c.one_minus_b1 * g;
+    const float v = c.b2 * nu[i] + c.one_minus_b2 * g * g;
     mu[i] = m;
     nu[i] = v;
     const float mh = m / c.bias_corr1;

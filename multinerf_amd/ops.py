@@ -1493,7 +1493,7 @@ def clip_adam(grad, params, mu, nu, begin, end, sqnorm, *, lr, b1, b2, eps, step
   for x, nm in ((grad, 'grad'), (params, 'params'), (mu, 'mu'), (nu, 'nu')):
     _chk(x, f32, nm)
   cfg = L.AdamCfg(float(lr), float(b1), float(b2), float(eps), float(1 - b1**step), float(1 - b2**step),
-                  float(grad_max_val), float(grad_max_norm))
+                  float(1 - b1), float(1 - b2), float(grad_max_val), float(grad_max_norm))
   _e = PROFILE.start()
   L.check(lib().mnr_clip_adam(C.byref(cfg), begin, end, _ptr(sqnorm), _ptr(grad), _ptr(params), _ptr(mu),
                               _ptr(nu), _stream()))

@@ -38,7 +38,7 @@ def test_library_exports_every_header_symbol():
     text = open(f).read()
     assert not any(n in text for n in dbg), f
     assert 'os.environ' not in text or os.path.basename(f) in ('build.py', 'dist.py', 'preflight.py', 'streams.py'), f
-  assert lib.mnr_abi_version() == 20
+  assert lib.mnr_abi_version() == 21
 
 
 def test_fp32_dense_debug_build_exports_the_same_abi():
@@ -52,7 +52,7 @@ def test_fp32_dense_debug_build_exports_the_same_abi():
   f32 = ctypes.CDLL(_lib.LIB_F32_PATH)
   for n in _lib._PROTOS:
     assert hasattr(f32, n) == (n not in _lib.F32_ABSENT), n
-  assert f32.mnr_abi_version() == 20
+  assert f32.mnr_abi_version() == 21
   assert not _lib.f32_active()
   with _lib.dense_f32():
     assert _lib.f32_active()

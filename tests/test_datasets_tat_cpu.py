@@ -218,7 +218,7 @@ def test_header_bindings_and_all_three_libraries_agree_on_mnr_image_ingest():
   for lib in libs:
     assert hasattr(lib, 'mnr_image_ingest')
     lib.mnr_abi_version.restype = ctypes.c_int
-    assert lib.mnr_abi_version() == 20
+    assert lib.mnr_abi_version() == 21
   with open(L.HEADER_PATH) as f:
     header = f.read()
   assert re.search(r'MNR_IMG_U8 = 0, MNR_IMG_F32 = 1', header) and L.IMG_DTYPE == {'uint8': 0, 'float32': 1}

@@ -203,7 +203,7 @@ def test_header_prototypes_and_libraries_agree_on_the_new_symbols():
   hip, hip_f32 = L.load(), C.CDLL(L.LIB_F32_PATH)
   for name in NEW_SYMBOLS:
     assert hasattr(hip, name) and hasattr(hip_f32, name), name
-  assert hip.mnr_abi_version() == 20 and hip_f32.mnr_abi_version() == 20
+  assert hip.mnr_abi_version() == 21 and hip_f32.mnr_abi_version() == 21
   # the ctypes mirrors have the layout the header declares (LP64: ints packed in fours, then 8-byte members)
   assert C.sizeof(L.SsimArgs) == 4 * 5 + 4 + 8 * 4 + 8 * 5
   assert C.sizeof(L.SqdiffArgs) == 4 * 7 + 4 + 8 * 5

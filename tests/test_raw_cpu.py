@@ -105,7 +105,7 @@ def test_header_bindings_and_both_libraries_agree_on_the_new_symbols():
     for name in NEW_SYMBOLS:
       assert hasattr(lib, name), (path, name)
     lib.mnr_abi_version.restype = ctypes.c_int
-    assert lib.mnr_abi_version() == 20
+    assert lib.mnr_abi_version() == 21
   with open(L.HEADER_PATH) as f:
     header = f.read()
   assert re.search(r'MNR_RAW_U16 = 0, MNR_RAW_F32 = 1', header) and L.RAW_DTYPE == {'uint16': 0, 'float32': 1}

@@ -127,7 +127,7 @@ def test_header_prototypes_and_libraries_agree_on_the_new_symbols():
   hip, hip_f32 = L.load(), C.CDLL(L.LIB_F32_PATH)
   for name in NEW_SYMBOLS:
     assert hasattr(hip, name) and hasattr(hip_f32, name), name
-  assert hip.mnr_abi_version() == 20 and hip_f32.mnr_abi_version() == 20
+  assert hip.mnr_abi_version() == 21 and hip_f32.mnr_abi_version() == 21
   # the struct the header declares and the ctypes mirror have the same size on the host side of the simulator
   assert C.sizeof(L.RobustArgs) == 8 * 2 + 4 * 4 + 8 * 2 + 8 * 3 + 8 + 8 * 7
-  assert sim_helpers.load_sim().mnr_abi_version() == 20
+  assert sim_helpers.load_sim().mnr_abi_version() == 21
