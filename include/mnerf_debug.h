@@ -39,8 +39,9 @@ int mnr_mlp_chain_set_max_wgs(int n);
  * see csrc/fused_mlp.hip) by every following mnr_mlp_chain_fwd / _bwd launch; NULL switches it off. */
 int mnr_debug_chain_timeline(unsigned long long* device_buffer);
 
-/* A/B switch: 1 (default) = four lanes per ray where a wave's 16 rays fit LDS, 0 = the lane-per-ray kernel everywhere.
- * Sums are associated differently in the two; both are held to the oracle by the same tolerances. */
+/* A/B switch of the compositing kernels (forward and level backward, csrc/render.hip): 1 (default) = the instantiation with
+ * four lanes per ray where a wave's 16 rays fit LDS, 0 = the one-lane-per-ray instantiation of the same body everywhere.
+ * Sums are associated differently in the two (blocked over the lanes); both are held to the oracle by the same tolerances. */
 int mnr_level_bwd_set_quad(int on);
 
 #ifdef __cplusplus

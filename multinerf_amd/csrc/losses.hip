@@ -119,20 +119,8 @@ __global__ void data_loss_kernel(int loss_type, float charb_padding, float loss_
         const float w = lm_c == 1 ? lm[b] : lm[b * 3 + ch];
         const float r = y - t;
         s_mse += w * r * r;                                   // train_utils.py:86-88
-        float dl, dd;
-        if (loss_type == MNR_LOSS_MSE) {                      // :90-92
-          dl = r * r;
-          dd = 2.0f * r;
-        } else if (loss_type == MNR_LOSS_CHARB) {             // :93-95
-          dl = sqrtf(r * r + charb_padding * charb_padding);
-          dd = r / dl;
-        } else {                                              // :96-103 rawnerf
-          const float yc = fminf(1.0f, y);
-          const float rc = yc - t;
-          const float sg = 1.0f / (1e-3f + yc);
-          dl = rc * rc * sg * sg;
-          dd = y < 1.0f ? 2.0f * rc * sg * sg : 0.0f;
-        }
+        float dd;
+        const float dl = ls_data_term(loss_type, y, t, charb_padding, dd);
         s_loss += w * dl;
         g = loss_mult * w * dd / denom;
       }

@@ -1,5 +1,5 @@
-// Per-ray pieces of the proposal losses (stepfun.py:30-86), shared by the stand-alone loss kernels (losses.hip) and the
-// fused per-level backward kernel (render.hip: level_bwd_kernel).
+// Per-ray pieces of the training losses (train_utils.py:85-103, stepfun.py:30-86), shared by the stand-alone loss kernels
+// (losses.hip) and the fused per-level backward kernel (render.hip).
 #pragma once
 
 #include "common.h"
@@ -12,7 +12,28 @@ __device__ __forceinline__ float ls_wave_sum(float v) {
   return v;
 }
 
-// lossfun_outer for one ray: the histogram (t[n+1], w[n]) against the envelope (te[ne+1], we[ne]; element i at
+// One channel's data-loss term (train_utils.py:90-103) for the rendered value y against the target t; dd = d term / d y.
+__device__ __forceinline__ float ls_data_term(int loss_type, float y, float t, float charb_padding, float& dd) {
+  const float rs = y - t;
+  float dl;
+  if (loss_type == MNR_LOSS_MSE) {                            // :90-92
+    dl = rs * rs;
+    dd = 2.0f * rs;
+  } else if (loss_type == MNR_LOSS_CHARB) {                   // :93-95
+    dl = sqrtf(rs * rs + charb_padding * charb_padding);
+    dd = rs / dl;
+  } else {                                                    // :96-103 rawnerf
+    const float yc = fminf(1.0f, y);
+    const float rc = yc - t;
+    const float sg = 1.0f / (1e-3f + yc);
+    dl = rc * rc * sg * sg;
+    dd = y < 1.0f ? 2.0f * rc * sg * sg : 0.0f;
+  }
+  return dl;
+}
+
+// lossfun_outer for one ray (interlevel_kernel and mnr_lossfun_outer in losses.hip): the histogram (t[n+1], w[n]) against
+// the envelope (te[ne+1], we[ne]; element i at
 // te[i * es] / we[i * es], so that the envelope may sit in LDS as [elem][ray]).  Writes, per fence-post k of t,
 // lo_f / hi_f (searchsorted indices as floats, stride S) and per interval either the scaled gradient factor
 // d loss / d w_outer (want_grad) or the loss term itself into g_or_loss (stride S); adds the loss terms to loss_sum.

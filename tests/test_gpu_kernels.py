@@ -1085,8 +1085,19 @@ def test_grid_laps_optimiser(ops):
                                                                 (30, True, True, 'sigmoid', 0.001, False),     # not a multiple of the 4 lanes per ray
                                                                 (128, False, True, 'safe_exp', 0.0, True)])
 def test_composite_fwd_bwd(ops, level_bwd_kernel, n, opaque, has_rgb, rgb_act, pad, noise):
+  _check_composite_fwd_bwd(ops, n, opaque, has_rgb, rgb_act, pad, noise)
+
+
+def test_composite_fwd_bwd_long_rays(ops):
+  """The launcher's own choice for rays too long for four lanes per ray: 288 samples with colour are the smallest multiple of
+  32 at which 16 rays exceed the quad kernels' LDS limit forward and backward, so one lane takes a ray, with fewer rays per
+  workgroup than lanes (8: idle lanes) and, at 37 rays, a ragged last workgroup.  Same oracle and
+  tolerances as test_composite_fwd_bwd (the lane-per-ray kernels before the two forms were merged met them at this shape)."""
+  _check_composite_fwd_bwd(ops, 288, True, True, 'sigmoid', 0.001, False, B=37)
+
+
+def _check_composite_fwd_bwd(ops, n, opaque, has_rgb, rgb_act, pad, noise, B=150):
   gen = torch.Generator().manual_seed(9)
-  B = 150
   raw_d = torch.randn((B, n), generator=gen) * 2
   raw_rgb = torch.randn((B, n, 3), generator=gen)
   tdist = torch.cumsum(torch.rand((B, n + 1), generator=gen) * 0.1 + 1e-3, -1) + 0.2
@@ -1216,8 +1227,19 @@ def test_level_bwd_fuses_losses_and_compositing_vjp(ops, level_bwd_kernel, mode,
   """mnr_level_bwd: data loss + interlevel | distortion loss + compositing VJP in ONE launch, against torch autograd of
   the oracle's composed objective (train_utils.py:72-159 on render.py:130-213), B_valid < B, with an upstream d / d weights
   (the Ref-NeRF normal losses' path) on top."""
+  _check_level_bwd(ops, mode, loss_type, lm_c, has_rgb, 137, 130, 64 if mode == 'interlevel' else 32, 32)
+
+
+@pytest.mark.parametrize('mode,loss_type,lm_c,has_rgb,n_ref', [('interlevel', 'charb', 1, False, 64), ('distortion', 'rawnerf', 3, True, 32)])
+def test_level_bwd_long_rays(ops, mode, loss_type, lm_c, has_rgb, n_ref):
+  """The same at 288 samples, where the launcher itself gives a ray to one lane (see test_composite_fwd_bwd_long_rays): 8 rays
+  per workgroup, 37 rays of which 33 are valid.  Same oracle and tolerances as above (met at this shape by the lane-per-ray
+  kernel before the two forms were merged)."""
+  _check_level_bwd(ops, mode, loss_type, lm_c, has_rgb, 37, 33, 288, n_ref)
+
+
+def _check_level_bwd(ops, mode, loss_type, lm_c, has_rgb, B, Bv, n, n_ref):
   gen = torch.Generator().manual_seed(21)
-  B, Bv, n, n_ref = 137, 130, 64 if mode == 'interlevel' else 32, 32
   raw_d = torch.randn((B, n), generator=gen) * 2
   raw_rgb = torch.randn((B, n, 3), generator=gen)
   sdist, _ = rand_stepfun(gen, B, n)

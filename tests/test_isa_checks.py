@@ -178,7 +178,7 @@ def test_fused_chain_weight_chunks_are_prefetched_not_waited_for_on_the_spot(rep
 def test_shipped_kernels_are_the_ones_validated_on_the_gpu(report):
   """profiles/r6_validated_isa.json holds digests of the device code of every kernel as it ran the round-6 GPU suite and
   bench (every kernel of round 5 unchanged, profiles/r5_validated_isa.json, plus cast_rays_ipe_tangent_bwd_kernel; act_tangent_kernel<true> and
-  clip_adam_kernel as re-validated with their leaf tests: cancellation-free act'', 1 - b from the host).  Host-side or simulator work must not change them; an intended kernel change re-validates on the GPU and rewrites
+  clip_adam_kernel as re-validated with their leaf tests: cancellation-free act'', 1 - b from the host; composite_fwd_kernel<LPR> / level_bwd_kernel<LPR> as re-validated when render.hip's four per-ray kernels became two bodies, profiles/r7_render_ab.md).  Host-side or simulator work must not change them; an intended kernel change re-validates on the GPU and rewrites
   the file (python tools/isa_report.py --write-digests profiles/r6_validated_isa.json)."""
   mod, _ = report
   want = json.load(open(VALIDATED))['kernels']
