@@ -6,6 +6,9 @@ rounding, so the layer activations, their 1-bit masks and the dX chain must agre
 The composed tests (tests/test_gpu_model.py) hold the fused path to the oracle.
 """
 
+import ctypes as C
+import re
+
 import numpy as np
 import pytest
 import torch
@@ -321,3 +324,497 @@ def test_chain_small_grids_change_no_bit(W, K0, depth, tiles, skip):
         assert torch.equal(x, y), f'max_wgs {max_wgs}: output {i} differs'
   finally:
     ops.L.check(dbg.mnr_mlp_chain_set_max_wgs(0))
+
+
+# ----------------------------------------------------------------------------- leaf tests: the three chain kernels against fp64
+# Called directly (no Model) on seeded tensors, every layer compared with plain fp64 torch on the kernel's OWN previous bf16
+# output, so that errors do not compound.  For a Dense layer with fan-in K, z the fp64 pre-activation and
+# mag = sum |a| |w| + |b|:
+#
+#     |got - relu(z)| <= 1/2 ulp_bf16(z) + (K + 1) 2^-23 mag
+#
+# the one rounding to bf16, plus a worst-case fp32 accumulation in any order at one fp32 ulp per addition (the rounding inside
+# an MFMA's 16-product sum is not documented as round-to-nearest).  The fp32 head: (W + 1) 2^-23 (sum |x| |w| + |b|).  The dX
+# layers: the layer formula with K = W and no bias.  Where the arithmetic is fully determined the comparison is bit for bit.
+
+_bf = torch.bfloat16
+_NAN = float('nan')
+_SENT = -7.0                                    # in every output buffer before the launch (a ReLU never writes it)
+_SENT_BITS = 0xA5
+
+
+def _i16(t):
+  return t.view(torch.int16)
+
+
+def _unpack_mask(bits, W):
+  """[M, W / 8] uint8 -> [M, W] bool: column n is bit n & 7 of byte n // 8 (include/mnerf.h)."""
+  return ((bits.cpu().int()[..., None] >> torch.arange(8)) & 1).reshape(bits.shape[0], W).bool()
+
+
+def _leaf_bound(z, mag, K):
+  _, ex = torch.frexp(z)                                       # |z| = m 2^ex, m in [0.5, 1): ulp_bf16(z) = 2^(ex - 8)
+  half_ulp = torch.where(z != 0, torch.ldexp(torch.ones_like(z), ex - 9), torch.zeros_like(z))
+  return half_ulp + (K + 1) * 2.0 ** -23 * mag
+
+
+def _leaf_ratio(got, ref, bound):
+  """max |got - ref| / bound in fp64 (NaN when anything is NaN, which then fails `<= 1`)."""
+  err = (got.double() - ref).abs()
+  return torch.where(err == 0, torch.zeros_like(err), err / bound).max().item()
+
+
+class _chain_switches:
+  """mnr_mlp_chain_set_deferred / mnr_mlp_chain_set_max_wgs (include/mnerf_debug.h), restored on the way out."""
+
+  def __enter__(self):
+    self.dbg = models.ops.L.debug()
+    return self
+
+  def set(self, defer=1, max_wgs=0):
+    models.ops.L.check(self.dbg.mnr_mlp_chain_set_deferred(defer))
+    models.ops.L.check(self.dbg.mnr_mlp_chain_set_max_wgs(max_wgs))
+
+  def __exit__(self, *exc):
+    self.set()
+    return False
+
+
+def _leaf_fwd_inputs(W, K0, ld_feat, pad, depth, skip, M, seed=31):
+  """Host tensors of one forward case.  Every padding element (columns >= K0 of feat, >= fan_in of a Bt) is NaN."""
+  g = torch.Generator().manual_seed(seed)
+  feat = torch.full((M, ld_feat), _NAN, dtype=_bf)
+  feat[:, :K0] = (torch.rand((M, K0), generator=g) * 2 - 1).to(_bf)
+  fan = [K0 if i == 0 else (W + K0 if (skip > 0 and i == skip) else W) for i in range(depth)]
+  Bt, bias = [], []
+  for i in range(depth):
+    w = torch.full((W, fan[i] + pad), _NAN, dtype=_bf)
+    w[:, :fan[i]] = ((torch.rand((W, fan[i]), generator=g) * 2 - 1) * (6.0 / fan[i]) ** 0.5).to(_bf)
+    Bt.append(w)
+    bias.append(0.05 * torch.randn((W,), generator=g))
+  wh = ((torch.rand((W,), generator=g) * 2 - 1) * 0.15).to(_bf)
+  bh = torch.full((1,), 0.0625 + 0.01)
+  return dict(W=W, K0=K0, depth=depth, skip=skip, M=M, fan=fan, feat=feat, Bt=Bt, bias=bias, wh=wh, bh=bh)
+
+
+def _leaf_fwd_run(inp, want_acts, want_bits, want_head):
+  """One mlp_chain_fwd launch.  want_acts / want_bits: one flag per layer.  Every output buffer has a guard row (element)
+  behind the M the kernel is given and starts as a sentinel; the guard must survive.  -> host copies (None: not requested)."""
+  ops = models.ops
+  M, W, depth = inp['M'], inp['W'], inp['depth']
+  acts = [torch.full((M + 1, W), _SENT, dtype=_bf, device='cuda') if w else None for w in want_acts]
+  bits = [torch.full((M + 1, W // 8), _SENT_BITS, dtype=torch.uint8, device='cuda') if w else None for w in want_bits]
+  head = torch.full((M + 1,), _SENT, device='cuda') if want_head else None
+  cut = lambda t: None if t is None else t[:M]
+  hk = dict(w_head=inp['wh'].cuda(), b_head=inp['bh'].cuda(), head_out=cut(head)) if want_head else {}
+  ops.mlp_chain_fwd(inp['feat'].cuda(), inp['K0'], [(w.cuda(), b.cuda()) for w, b in zip(inp['Bt'], inp['bias'])], M=M, W=W,
+                    acts=[cut(a) for a in acts], bits=[cut(b) for b in bits], skip_layer=inp['skip'], **hk)
+  torch.cuda.synchronize()
+  for a in acts:
+    assert a is None or bool((a[M] == _SENT).all()), 'activation guard row'
+  for b in bits:
+    assert b is None or bool((b[M] == _SENT_BITS).all()), 'mask guard row'
+  assert head is None or head[M].item() == _SENT, 'head guard element'
+  host = lambda t: None if t is None else t[:M].cpu().clone()
+  return dict(acts=[host(a) for a in acts], bits=[host(b) for b in bits], head=host(head))
+
+
+def _leaf_same(ref, got, what):
+  """Every output `got` has is `ref`'s, bit for bit."""
+  for i, (x, y) in enumerate(zip(ref['acts'], got['acts'])):
+    assert y is None or torch.equal(_i16(x), _i16(y)), f'{what}: activation {i}'
+  for i, (x, y) in enumerate(zip(ref['bits'], got['bits'])):
+    assert y is None or torch.equal(x, y), f'{what}: mask bits {i}'
+  assert got['head'] is None or torch.equal(ref['head'].view(torch.int32), got['head'].view(torch.int32)), f'{what}: head'
+
+
+def _leaf_fwd_check(inp, out, rows=None):
+  """Every layer, its masks and the head of a full run against fp64 -> worst error / bound per output."""
+  W, K0, depth = inp['W'], inp['K0'], inp['depth']
+  sel = slice(None) if rows is None else rows
+  f = inp['feat'][:, :K0].double()[sel]
+  ratios = []
+  for i in range(depth):
+    a = f if i == 0 else out['acts'][i - 1].double()[sel]
+    if inp['skip'] > 0 and i == inp['skip']:
+      a = torch.cat([a, f], dim=1)                                   # [x | features] (models.py:458-459)
+    w, b = inp['Bt'][i][:, :inp['fan'][i]].double(), inp['bias'][i].double()
+    z = a @ w.T + b
+    mag = a.abs() @ w.abs().T + b.abs()
+    got = out['acts'][i][sel]
+    ratios.append(_leaf_ratio(got, z.clamp(min=0), _leaf_bound(z, mag, inp['fan'][i])))
+    assert torch.equal(_unpack_mask(out['bits'][i], W)[sel], got > 0), f'mask bits of layer {i} are not (activation > 0)'
+    assert not bool((_i16(got) == -32768).any()), f'layer {i} stores a negative zero'
+  x, wh, bh = out['acts'][-1].double()[sel], inp['wh'].double(), inp['bh'].double()
+  ratios.append(_leaf_ratio(out['head'][sel], x @ wh + bh, (W + 1) * 2.0 ** -23 * (x.abs() @ wh.abs() + bh.abs())))
+  return ratios
+
+
+def _leaf_fwd_variants(depth):
+  """The output combinations fm_copy_out_dispatch (last layer, and every layer with the copy-out in front of the pass) and
+  fm_layer_mfma_defer (the copy-out inside the next pass) distinguish: (acts per layer, bits per layer, head)."""
+  yes, no = [True] * depth, [False] * depth
+  last = [i == depth - 1 for i in range(depth)]
+  v = {'acts only': (yes, no, False), 'bits only': (no, yes, False), 'head only': (no, no, True),
+       'acts of the last layer, no head': (last, no, False), 'acts + head': (yes, no, True), 'bits + head': (no, yes, True),
+       'acts + bits, no head': (yes, yes, False)}
+  if depth >= 2:
+    hole = [i != (depth // 2 if depth >= 3 else 0) for i in range(depth)]
+    v['one layer with neither output'] = (hole, hole, True)
+  return v
+
+
+@pytest.mark.parametrize('W,K0,ld_feat,pad,depth,skip,M', [
+    (128, 64, 64, 0, 1, 0, 256),        # one K step (only the stream's prologue), one layer, one tile
+    (128, 192, 200, 8, 3, 1, 768),      # odd step count, padded strides, skip right after layer 0
+    (256, 128, 128, 0, 8, 7, 512),      # maximum depth, skip into the last layer
+    (256, 576, 576, 8, 2, 0, 256),      # long layer-0 stream (9 steps)
+    (256, 64, 72, 0, 4, 2, 256),        # skip with the smallest feature segment
+])
+def test_chain_leaf_fwd(W, K0, ld_feat, pad, depth, skip, M):
+  """mlp_chain_fwd_kernel: every layer, its 1-bit masks and the head against fp64; every output variant, the copy-out in
+  front of the pass (mnr_mlp_chain_set_deferred(0)) and a capped grid bit for bit against the full default run."""
+  inp = _leaf_fwd_inputs(W, K0, ld_feat, pad, depth, skip, M)
+  yes = [True] * depth
+  with _chain_switches() as sw:
+    ref = _leaf_fwd_run(inp, yes, yes, True)
+    ratios = _leaf_fwd_check(inp, ref)
+    print(f'chain_leaf_fwd W={W} K0={K0} depth={depth} skip={skip} M={M}: worst error / bound per layer '
+          + ' '.join(f'{r:.3f}' for r in ratios[:-1]) + f', head {ratios[-1]:.3f}')
+    assert all(r <= 1.0 for r in ratios), ratios
+    for a in ref['acts']:
+      assert 0.2 < (a > 0).float().mean().item() < 0.8                 # (not a comparison of zeros)
+    for defer in (1, 0):
+      sw.set(defer=defer)
+      if defer == 0:
+        _leaf_same(ref, _leaf_fwd_run(inp, yes, yes, True), 'defer 0, everything')
+      for name, (wa, wb, whd) in _leaf_fwd_variants(depth).items():
+        _leaf_same(ref, _leaf_fwd_run(inp, wa, wb, whd), f'defer {defer}, {name}')
+    if M > 256:                         # M = 768 on two workgroups: one walks two tiles, the other one
+      sw.set(defer=1, max_wgs=2 if M == 768 else 1)
+      _leaf_same(ref, _leaf_fwd_run(inp, yes, yes, True), 'capped grid')
+
+
+def test_chain_leaf_fwd_edge_values():
+  """Zeros and one non-finite feature: an output that is exactly zero (zero features and a zero bias of either sign, a unit
+  with an all-zero weight row and zero bias) is the bit pattern 0x0000 with mask bit 0, and a +inf in one feature row touches
+  no other row of the activations, masks or head."""
+  W, K0, M = 128, 64, 256
+  inp = _leaf_fwd_inputs(W, K0, K0, 0, 2, 0, M, seed=32)
+  zrows = slice(32, 64)
+  inp['feat'][zrows] = 0
+  inp['bias'][0][0], inp['bias'][0][1] = 0.0, -0.0
+  inp['Bt'][0][5], inp['bias'][0][5] = 0, 0.0
+  inp['Bt'][1][7], inp['bias'][1][7] = 0, -0.0
+  out = _leaf_fwd_run(inp, [True] * 2, [True] * 2, True)
+  ratios = _leaf_fwd_check(inp, out)
+  print('chain_leaf_fwd_edge_values: worst error / bound ' + ' '.join(f'{r:.3f}' for r in ratios))
+  assert all(r <= 1.0 for r in ratios), ratios
+  # zero features: layer 0 is relu(bias) rounded once, exactly
+  want = torch.where(inp['bias'][0] > 0, inp['bias'][0], torch.zeros(())).to(_bf).expand(32, W)
+  assert torch.equal(_i16(out['acts'][0][zrows]), _i16(want))
+  m0, m1 = _unpack_mask(out['bits'][0], W), _unpack_mask(out['bits'][1], W)
+  for what, a, m in (('zero bias', out['acts'][0][zrows, 0], m0[zrows, 0]), ('negative-zero bias', out['acts'][0][zrows, 1], m0[zrows, 1]),
+                     ('zero unit of layer 0', out['acts'][0][:, 5], m0[:, 5]), ('zero unit of layer 1', out['acts'][1][:, 7], m1[:, 7])):
+    assert bool((_i16(a) == 0).all()) and not bool(m.any()), what
+  # row isolation
+  row = 100
+  inp['feat'][row, 3] = float('inf')
+  bad = _leaf_fwd_run(inp, [True] * 2, [True] * 2, True)
+  keep = torch.arange(M) != row
+  for i in range(2):
+    assert torch.equal(_i16(bad['acts'][i])[keep], _i16(out['acts'][i])[keep]), f'activation {i} outside the poisoned row'
+    assert torch.equal(bad['bits'][i][keep], out['bits'][i][keep]), f'mask bits {i} outside the poisoned row'
+  assert torch.equal(bad['head'].view(torch.int32)[keep], out['head'].view(torch.int32)[keep]), 'head outside the poisoned row'
+  assert not bool(torch.isfinite(bad['acts'][0][row].float()).all())               # (the poison arrived)
+
+
+def _leaf_masks(M, W, depth, g):
+  """The test's own mask bytes (no forward pass): random, with all-zero and all-one rows, rows of single-bit bytes and rows
+  with one single-bit byte, in the first and in the last tile."""
+  out = []
+  for i in range(depth):
+    b = torch.randint(0, 256, (M, W // 8), generator=g, dtype=torch.uint8)
+    for base in (0, M - 32):
+      b[base], b[base + 1] = 0, 0xFF
+      for e in range(8):
+        b[base + 2 + e] = 1 << e
+        b[base + 10 + e] = 0
+        b[base + 10 + e, (3 * e + i) % (W // 8)] = 1 << e
+    out.append(b)
+  return out
+
+
+def _leaf_bwd_run(W, M, masks, Bw, gh=None, wh=None, dY_in=None, store_last=True):
+  ops = models.ops
+  depth = len(masks)
+  dY = [torch.full((M + 1, W), -_SENT, dtype=_bf, device='cuda') if (i < depth - 1 or store_last) else None for i in range(depth)]
+  dev = lambda t: None if t is None else t.cuda()
+  ops.mlp_chain_bwd(dev(gh), dev(wh), [b.cuda() for b in masks], [dev(w) for w in Bw], [None if d is None else d[:M] for d in dY],
+                    M=M, W=W, dY_in=dev(dY_in))
+  torch.cuda.synchronize()
+  for d in dY:
+    assert d is None or bool((d[M] == -_SENT).all()), 'dY guard row'
+  return [None if d is None else d[:M].cpu().clone() for d in dY]
+
+
+def _leaf_bwd_check(W, masks, Bw, dY, top):
+  """dY[i - 1] against fp64 on the kernel's own dY[i] (`top` for the last layer) -> worst error / bound per layer, last first."""
+  depth = len(masks)
+  ratios = []
+  for i in reversed(range(1, depth)):
+    src = (top if i == depth - 1 else dY[i]).double()
+    w = Bw[i][:, :W].double()
+    z, mag = src @ w.T, src.abs() @ w.abs().T
+    keep = _unpack_mask(masks[i - 1], W)
+    got = dY[i - 1]
+    ratios.append(_leaf_ratio(got, torch.where(keep, z, torch.zeros_like(z)), _leaf_bound(z, mag, W)))
+    assert bool((_i16(got)[~keep] == 0).all()), f'dY[{i - 1}]: a masked element is not +0'
+    # bit by bit: what is stored is non-zero exactly where the mask bit is set (and the fp64 value is not zero itself: rows
+    # whose gradient or whose masks above are all zero)
+    live = keep & (z.abs() > 1e-30)
+    assert torch.equal(got != 0, live), f'dY[{i - 1}]: stored zeros and mask bits of layer {i - 1} disagree'
+    assert live.float().mean().item() > 0.25
+  return ratios
+
+
+@pytest.mark.parametrize('W,depth,M', [(128, 1, 256), (128, 3, 768), (256, 8, 256), (256, 2, 768)])
+def test_chain_leaf_bwd(W, depth, M):
+  """mlp_chain_bwd_kernel on masks of the test's own: the rank-1 start bit for bit, every dX layer against fp64, masked elements
+  exactly +0 and stored zeros agreeing with the mask bit by bit (bit order, byte order, which layer's masks are read); without
+  dY[last], from dY_in, with the copy-out in front of the pass and on a capped grid bit for bit."""
+  g = torch.Generator().manual_seed(41)
+  masks = _leaf_masks(M, W, depth, g)
+  Bw = [None]
+  for i in range(1, depth):
+    w = torch.full((W, W + 8), _NAN, dtype=_bf)
+    w[:, :W] = ((torch.rand((W, W), generator=g) * 2 - 1) * (6.0 / W) ** 0.5).to(_bf)
+    Bw.append(w)
+  wh = (torch.rand((W,), generator=g) * 2 - 1) * 0.15
+  gh = torch.randn((M,), generator=g) * 0.01
+  gh[40:48] = torch.tensor([0.0, -0.0, 1e4, -1e4, 1e-20, -1e-20, 0.0, 1e4])
+  gh[M - 48:M - 44] = torch.tensor([1e4, 1e-20, 0.0, -1e4])
+  start = torch.where(_unpack_mask(masks[-1], W), (gh[:, None] * wh[None, :]).to(_bf), torch.zeros((), dtype=_bf))
+  with _chain_switches() as sw:
+    ref = _leaf_bwd_run(W, M, masks, Bw, gh, wh)
+    assert torch.equal(_i16(ref[-1]), _i16(start)), 'rank-1 start: dY[last] is not bf16(fp32(g) fp32(w)) under the mask'
+    ratios = _leaf_bwd_check(W, masks, Bw, ref, ref[-1])
+    print(f'chain_leaf_bwd W={W} depth={depth} M={M}: worst error / bound per dX layer (last first) ' + ' '.join(f'{r:.3f}' for r in ratios))
+    assert all(r <= 1.0 for r in ratios), ratios
+
+    def same(got, what):
+      for i, (x, y) in enumerate(zip(ref, got)):
+        assert y is None or torch.equal(_i16(x), _i16(y)), f'{what}: dY[{i}]'
+
+    same(_leaf_bwd_run(W, M, masks, Bw, gh, wh, store_last=False), 'without dY[last]')
+    sw.set(defer=0)
+    same(_leaf_bwd_run(W, M, masks, Bw, gh, wh), 'defer 0')
+    same(_leaf_bwd_run(W, M, masks, Bw, gh, wh, store_last=False), 'defer 0 without dY[last]')
+    if M > 256:
+      sw.set(defer=1, max_wgs=2)
+      same(_leaf_bwd_run(W, M, masks, Bw, gh, wh), 'capped grid')
+    if (W, depth) in ((128, 3), (256, 2)):
+      # the dY_in start (an MLP with heads; the Ref-NeRF tangent chain): a dY_last of the caller's
+      sw.set()
+      dy_in = torch.randn((M, W), generator=g).mul_(0.01).to(_bf)
+      dy_in[40], dy_in[41] = 1e4, -1e-20
+      ref_in = _leaf_bwd_run(W, M, masks, Bw, dY_in=dy_in, store_last=False)
+      ratios = _leaf_bwd_check(W, masks, Bw, ref_in, dy_in)
+      print(f'chain_leaf_bwd W={W} depth={depth} M={M} from dY_in: ' + ' '.join(f'{r:.3f}' for r in ratios))
+      assert all(r <= 1.0 for r in ratios), ratios
+      for defer, max_wgs in ((0, 0), (1, 2)):
+        sw.set(defer=defer, max_wgs=max_wgs)
+        got = _leaf_bwd_run(W, M, masks, Bw, dY_in=dy_in, store_last=False)
+        for i in range(depth - 1):
+          assert torch.equal(_i16(ref_in[i]), _i16(got[i])), f'dY_in start, defer {defer}, max_wgs {max_wgs}: dY[{i}]'
+
+
+def _group_major_columns(K, L):
+  """(source column of the [2KL] feature row / kernel row, group-major column) pairs of include/mnerf.h:
+  column g*192 + dl*2K + s*K + k  =  kernel row s*K*L + (4g + dl)*K + k."""
+  G = 192
+  src, dst = [], []
+  for gi in range(L // 4):
+    for dl in range(4):
+      for s in range(2):
+        for k in range(K):
+          src.append(s * K * L + (4 * gi + dl) * K + k)
+          dst.append(gi * G + dl * 2 * K + s * K + k)
+  return torch.tensor(src), torch.tensor(dst)
+
+
+@pytest.mark.parametrize('K,min_deg,max_deg,W,n,B,ray_shape,contract,no_int', [
+    (21, 0, 12, 256, 48, 16, 'cone', True, False),          # rays straddle the 256-row tiles
+    (3, 0, 16, 128, 32, 8, 'cylinder', False, False),
+    (3, 2, 6, 128, 32, 8, 'cone', True, False),             # non-zero min_deg, single group
+    (24, 0, 8, 256, 64, 4, 'cone', False, False),           # no pad slots (8K = 192)
+    (1, 0, 4, 128, 256, 1, 'cylinder', True, True),         # the lower edge of K; disable_integration
+])
+def test_chain_leaf_fwd_ipe(K, min_deg, max_deg, W, n, B, ray_shape, contract, no_int):
+  """mlp_chain_fwd_ipe_kernel with a group-major Bt[0] the test builds itself from a row-major kernel: depth 1 against the fp64
+  product of cast_rays_ipe's bf16 rows (pinned to the oracle by test_cast_rays_ipe), and depth 3 with its head bit for bit
+  against mlp_chain_fwd on the feature matrix the test permutes into group-major order."""
+  ops = models.ops
+  L, M = max_deg - min_deg, B * n
+  nfeat, ld_g = 2 * K * L, (L // 4) * 192
+  g = torch.Generator().manual_seed(51)
+  basis = torch.nn.functional.normalize(torch.randn((K, 3), generator=g), dim=-1).cuda()
+  origins = (torch.randn((B, 3), generator=g) * 0.3).cuda()
+  directions = torch.nn.functional.normalize(torch.randn((B, 3), generator=g), dim=-1).cuda() * 1.3
+  radii = (0.002 + 0.002 * torch.rand((B,), generator=g)).cuda()
+  tdist = torch.cumsum(0.02 + torch.rand((B, n + 1), generator=g) * (12.0 / n), dim=-1).cuda().contiguous()   # in and beyond the unit ball
+  kw = dict(ray_shape=ray_shape, warp_contract=contract, min_deg=min_deg, max_deg=max_deg, disable_integration=no_int)
+  kernel = ((torch.rand((nfeat, W), generator=g) * 2 - 1) * (6.0 / nfeat) ** 0.5).to(_bf)          # row-major: rows = inputs
+  src, dst = _group_major_columns(K, L)
+  Bt0 = torch.full((W, ld_g + 8), _NAN, dtype=_bf)
+  Bt0[:, :ld_g] = 0
+  Bt0[:, dst] = kernel.T[:, src]
+  biases = [0.05 * torch.randn((W,), generator=g) for _ in range(3)]
+  deeper = [((torch.rand((W, W), generator=g) * 2 - 1) * (6.0 / W) ** 0.5).to(_bf) for _ in range(2)]
+  wh = ((torch.rand((W,), generator=g) * 2 - 1) * 0.15).to(_bf)
+  bh = torch.full((1,), 0.0725)
+  feat = ops.cast_rays_ipe(tdist, origins, directions, radii, basis, ld_feat=nfeat, **kw)
+  # depth 1
+  act = torch.full((M + 1, W), _SENT, dtype=_bf, device='cuda')
+  ops.mlp_chain_fwd_ipe(tdist, origins, directions, radii, basis, [(Bt0.cuda(), biases[0].cuda())], M=M, W=W, act_last=act[:M], **kw)
+  torch.cuda.synchronize()
+  assert bool((act[M] == _SENT).all()), 'activation guard row'
+  a, w, b = feat.cpu().double(), kernel.double(), biases[0].double()
+  z, mag = a @ w + b, a.abs() @ w.abs() + b.abs()
+  ratio = _leaf_ratio(act[:M].cpu(), z.clamp(min=0), _leaf_bound(z, mag, nfeat))
+  print(f'chain_leaf_fwd_ipe K={K} degrees [{min_deg}, {max_deg}) W={W} n={n} {ray_shape}: layer 0 worst error / bound {ratio:.3f}')
+  assert ratio <= 1.0
+  assert 0.1 < (act[:M] > 0).float().mean().item() < 0.9 and a.abs().max().item() > 0.5
+  # depth 3 with the head: the grouped route on the same bf16 features, the same operand, the same order over K
+  feat_g = torch.zeros((M, ld_g), dtype=_bf)
+  feat_g[:, dst] = feat.cpu()[:, src]
+  layers = [(Bt0.cuda(), biases[0].cuda())] + [(deeper[i].cuda(), biases[i + 1].cuda()) for i in range(2)]
+  outs = []
+  for ipe in (True, False):
+    x = torch.full((M + 1, W), _SENT, dtype=_bf, device='cuda')
+    h = torch.full((M + 1,), _SENT, device='cuda')
+    hk = dict(w_head=wh.cuda(), b_head=bh.cuda(), head_out=h[:M])
+    if ipe:
+      ops.mlp_chain_fwd_ipe(tdist, origins, directions, radii, basis, layers, M=M, W=W, act_last=x[:M], **hk, **kw)
+    else:
+      ops.mlp_chain_fwd(feat_g.cuda(), ld_g, layers, M=M, W=W, acts=[None, None, x[:M]], **hk)
+    torch.cuda.synchronize()
+    assert bool((x[M] == _SENT).all()) and h[M].item() == _SENT, 'guard row'
+    outs.append((x[:M].cpu(), h[:M].cpu()))
+  assert torch.equal(_i16(outs[0][0]), _i16(outs[1][0])), 'act_last: in-kernel IPE against the grouped feature matrix'
+  assert torch.equal(outs[0][1].view(torch.int32), outs[1][1].view(torch.int32)), 'head: in-kernel IPE against the grouped feature matrix'
+  assert outs[0][1].abs().max().item() > 0 and bool(torch.isfinite(outs[0][1]).all())
+
+
+def test_chain_leaf_rejects_bad_arguments():
+  """One call per MNR_CHECK_ARG family of the three launchers, on the args structs themselves (ops.py's own assertions would
+  intercept most of them): each raises with the launcher's message, and no output buffer is touched."""
+  ops = models.ops
+  Lb = ops.L
+  lib = ops.lib()
+  M, W, K0, n = 256, 128, 64, 32
+  z = lambda shape, dt=_bf: torch.zeros(shape, dtype=dt, device='cuda')
+  t = dict(feat=z((M, K0)), Bt0=z((W, 192)), Bt1=z((W, W + K0)), bias0=z((W + 4,), torch.float32), bias1=z((W,), torch.float32),
+           wh=z((W,)), bh=z((1,), torch.float32), whf=z((W,), torch.float32), gh=z((M,), torch.float32), dY_in=z((M, W)),
+           tdist=torch.linspace(0.1, 3.0, n + 1).repeat(M // n, 1).contiguous().cuda(), o=z((M // n, 3), torch.float32),
+           d=torch.ones((M // n, 3)).cuda(), r=torch.full((M // n,), 0.01).cuda(), basis=torch.eye(3).cuda())
+  outs = dict(acts0=z((M, W)), acts1=z((M, W)), bits0=z((M, W // 8), torch.uint8), bits1=z((M, W // 8), torch.uint8),
+              head=z((M,), torch.float32), dY0=z((M, W)), dY1=z((M, W)))
+  for o in outs.values():
+    o.fill_(3)
+  p = lambda x: x.data_ptr()
+
+  def fwd():
+    a = Lb.MlpChainFwdArgs()
+    a.M, a.W, a.depth, a.skip_layer = M, W, 2, 0
+    a.feat, a.ld_feat, a.K0 = p(t['feat']), K0, K0
+    a.Bt[0], a.ldb[0], a.bias[0] = p(t['Bt0']), 192, p(t['bias0'])
+    a.Bt[1], a.ldb[1], a.bias[1] = p(t['Bt1']), W + K0, p(t['bias1'])
+    a.acts[0], a.acts[1], a.bits[0], a.bits[1] = p(outs['acts0']), p(outs['acts1']), p(outs['bits0']), p(outs['bits1'])
+    a.w_head, a.b_head, a.head_out = p(t['wh']), p(t['bh']), p(outs['head'])
+    return a
+
+  def bwd():
+    a = Lb.MlpChainBwdArgs()
+    a.M, a.W, a.depth = M, W, 2
+    a.g_head, a.w_head = p(t['gh']), p(t['whf'])
+    a.bits[0], a.bits[1] = p(outs['bits0']), p(outs['bits1'])
+    a.Bw[1], a.ldb[1] = p(t['Bt1']), W + K0
+    a.dY[0], a.dY[1] = p(outs['dY0']), p(outs['dY1'])
+    return a
+
+  def ipe_chain():
+    a = fwd()
+    a.feat, a.ld_feat, a.K0 = None, 0, 0
+    a.acts[0], a.bits[0], a.bits[1] = None, None, None
+    return a
+
+  def ipe_rays():
+    q = Lb.ChainIpeArgs()
+    q.cfg = Lb.IpeCfg(0, 1, 0, 3, 0, 4)
+    q.n = n
+    q.tdist, q.origins, q.directions, q.radii, q.basis = p(t['tdist']), p(t['o']), p(t['d']), p(t['r']), p(t['basis'])
+    return q
+
+  calls = {
+      'mnr_mlp_chain_fwd': lambda a, q: lib.mnr_mlp_chain_fwd(C.byref(a), ops._stream()),
+      'mnr_mlp_chain_bwd': lambda a, q: lib.mnr_mlp_chain_bwd(C.byref(a), ops._stream()),
+      'mnr_mlp_chain_fwd_ipe': lambda a, q: lib.mnr_mlp_chain_fwd_ipe(C.byref(a), C.byref(q), ops._stream()),
+  }
+  make = {'mnr_mlp_chain_fwd': fwd, 'mnr_mlp_chain_bwd': bwd, 'mnr_mlp_chain_fwd_ipe': ipe_chain}
+
+  def sa(**kv):                              # set fields; name_i addresses element i of an array field
+    def mut(a, q):
+      for k, v in kv.items():
+        tgt, k = (q, k[2:]) if k.startswith('q_') else (a, k)
+        el = re.fullmatch(r'(.+)_(\d)', k)
+        if el:
+          getattr(tgt, el.group(1))[int(el.group(2))] = v
+        else:
+          setattr(tgt, k, v)
+    return mut
+
+  def cfg(**kv):
+    def mut(a, q):
+      for k, v in kv.items():
+        setattr(q.cfg, k, v)
+    return mut
+
+  cases = []
+  for who in calls:                          # fm_check_common
+    cases += [(who, sa(M=0), f'{who}: M=0 must be a positive multiple of 256'),
+              (who, sa(M=255 + 1 - 2), f'{who}: M=254 must be a positive multiple of 256'),
+              (who, sa(W=192), f'{who}: width 192 is not 128 or 256'),
+              (who, sa(depth=0), f'{who}: depth 0 out of range'),
+              (who, sa(depth=9), f'{who}: depth 9 out of range')]
+  who = 'mnr_mlp_chain_fwd'
+  cases += [(who, sa(K0=96), 'feature matrix needs K0'),
+            (who, sa(ld_feat=K0 - 8), 'feature matrix needs K0'),
+            (who, sa(skip_layer=1, ldb_1=W + K0 - 8), 'skip_layer 1 needs 0 < skip_layer < depth and an operand of W \\+ K0 columns'),
+            (who, sa(skip_layer=2), 'skip_layer 2 needs 0 < skip_layer < depth'),
+            (who, sa(bias_0=p(t['bias0'][1:])), 'bias\\[0\\] must be 16-byte aligned'),
+            (who, sa(head_out=None), 'head needs head_out')]
+  who = 'mnr_mlp_chain_bwd'
+  cases += [(who, sa(dY_0=None), 'dY\\[0\\] missing'),
+            (who, sa(dY_in=p(t['dY_in'])), 'with dY_in the last dY is the input itself'),
+            (who, sa(bits_0=None), 'layer 0 needs its ReLU mask bits'),
+            (who, sa(ldb_1=W - 8), 'layer 1 operand')]
+  who = 'mnr_mlp_chain_fwd_ipe'
+  cases += [(who, cfg(max_deg=6), 'degrees=6 \\(a multiple of 4\\) out of range'),
+            (who, cfg(basis_k=25), 'basis_k=25 \\(1..24\\)'),
+            (who, sa(skip_layer=1), 'no skip concat'),
+            (who, sa(bits_1=p(outs['bits1'])), 'inference only'),
+            (who, sa(q_n=48), 'M is not a whole number of rays'),
+            (who, sa(w_head=None, acts_1=None), 'needs a head \\(with head_out\\) or acts\\[depth-1\\]')]
+  for who, mut, msg in cases:
+    a, q = make[who](), ipe_rays()
+    mut(a, q)
+    with pytest.raises(ValueError, match=msg):
+      Lb.check(calls[who](a, q))
+    torch.cuda.synchronize()
+    for name, o in outs.items():
+      assert bool((o == 3).all()), f'{who} ({msg}): touched {name}'
+  # (the structs above are accepted as they stand: every rejection is the mutated field's)
+  for who in calls:
+    Lb.check(calls[who](make[who](), ipe_rays()))
+  torch.cuda.synchronize()

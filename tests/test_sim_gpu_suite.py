@@ -50,6 +50,15 @@ def test_in_kernel_ipe_chain_passes_on_the_simulator():
   assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail, tail
 
 
+def test_chain_leaf_tests_pass_on_the_simulator():
+  """The three chain kernels against fp64 at free shapes (tests/test_gpu_chain.py, `chain_leaf`): every layer, mask bit and
+  head value under the derived bounds, the output variants, the copy-out in front of the pass and capped grids bit for bit,
+  the dX chain on masks of the test's own, the in-kernel IPE producer on a hand-built group-major operand, and the launchers'
+  argument checks (~60 s of simulator time on four workers)."""
+  tail = _child(['tests/test_gpu_chain.py', '-k', 'chain_leaf'], 900)
+  assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail, tail
+
+
 def test_sampling_gradient_kernels_pass_on_the_simulator():
   """Model.stop_level_grad = False (round 5): mnr_resample_level_bwd, mnr_cast_rays_ipe_bwd, mnr_sdist_bwd + the level kernels'
   g_x output against the oracle's autograd, and the composed train steps (at the simulator's reduced widths), with the code of
