@@ -13,6 +13,11 @@ volume over the box (`mesh.tsdf_mesh`, csrc/tsdf.hip), whose zero set between ob
 to choose; rays with opacity below --acc_threshold carve free space; colours come from the renders.  --tsdf_trunc, the
 truncation in grid spacings, is a decision: larger closes thin gaps and thickens thin structures.  Perspective cameras only.
 
+--min_component_faces / --keep_largest drop small connected components (`mesh.filter_components`: floaters are little closed
+shells of their own) and --simplify F merges the vertices of every cube of F grid spacings into one, placed by the quadric
+error of the faces around it (`mesh.simplify`, csrc/meshclean.hip); components first, then simplification, with either method.
+With all three at their defaults nothing of this runs and the file is the one written before.
+
   python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
       --resolution 512 --density_threshold 10 --out garden.ply
   python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
@@ -50,6 +55,9 @@ def parse_args(argv):
   ap.add_argument('--tsdf_stride', type=int, default=1, help='render every n-th camera')
   ap.add_argument('--tsdf_depth', choices=('distance_median', 'distance_mean'), default='distance_median')
   ap.add_argument('--acc_threshold', type=float, default=0.5, help='rays with less opacity are empty: they carve free space')
+  ap.add_argument('--min_component_faces', type=int, default=0, help='drop connected components with fewer faces (0: keep all)')
+  ap.add_argument('--keep_largest', type=int, default=0, help='keep only this many components with the most faces (0: keep all)')
+  ap.add_argument('--simplify', type=float, default=0., help='vertex clustering with a cell of this many grid spacings (0: off)')
   # `--bbox -1,-1,-1,1,1,1`: argparse takes a value that starts with '-' and is no plain number for an option; hand it over as --bbox=...
   argv = list(argv)
   for i in range(len(argv) - 1):
@@ -63,7 +71,36 @@ def parse_args(argv):
       raise ValueError
   except ValueError:
     raise SystemExit(f'extract_mesh.py: --bbox {args.bbox!r} must be six numbers x0,y0,z0,x1,y1,z1') from None
+  if args.min_component_faces < 0 or args.keep_largest < 0 or not (0. <= args.simplify < float('inf')):
+    raise SystemExit('extract_mesh.py: --min_component_faces, --keep_largest and --simplify must not be negative')
   return args, box
+
+
+def _format_stats(stats):
+  return ', '.join(f'{k} {v:.6g}' if isinstance(v, float) else f'{k} {v}' for k, v in stats.items())
+
+
+def _clean_up_seconds(args, t_comp, t_simp):
+  if args.min_component_faces == 0 and args.keep_largest == 0 and args.simplify == 0.:
+    return ''
+  return f', components {t_comp:.3f}, simplify {t_simp:.3f}'
+
+
+def clean_up(args, result, spacing, timed):
+  """(the mesh after --min_component_faces / --keep_largest and --simplify, seconds of the components step, seconds of the
+  simplification); the mesh itself and (0, 0) when all three are at their defaults.  Prints the statistics before and after."""
+  if args.min_component_faces == 0 and args.keep_largest == 0 and args.simplify == 0.:
+    return result, 0., 0.
+  report = lambda label, m: print(f'{label}: mesh_stats: {_format_stats(mesh.mesh_stats(m["vertices"], m["faces"]))}; '
+                                  f'components {mesh.component_stats(m)["count"]}')
+  report('before clean-up', result)
+  t_comp = t_simp = 0.
+  if args.min_component_faces > 0 or args.keep_largest > 0:
+    result, t_comp = timed(lambda: mesh.filter_components(result, min_faces=args.min_component_faces, keep_largest=args.keep_largest))
+  if args.simplify > 0.:
+    result, t_simp = timed(lambda: mesh.simplify(result, args.simplify * spacing))
+  report('after clean-up', result)
+  return result, t_comp, t_simp
 
 
 def main():
@@ -98,12 +135,14 @@ def main():
   if not args.no_colors:
     colors, t_col = timed(lambda: mesh.vertex_colors(model, verts, normals, args.std * spacing, args.chunk))
   result = dict(vertices=verts, normals=normals, faces=faces, colors=colors)
+  result, t_comp, t_simp = clean_up(args, result, spacing, timed)
+  verts, faces = result['vertices'], result['faces']
   os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
   _, t_write = timed(lambda: mesh.write_ply(out, result))
   stats = mesh.mesh_stats(verts, faces)
-  print('mesh_stats: ' + ', '.join(f'{k} {v:.6g}' if isinstance(v, float) else f'{k} {v}' for k, v in stats.items()))
+  print('mesh_stats: ' + _format_stats(stats))
   print(f'seconds: grid query {t_grid:.3f} ({field.numel() / max(t_grid, 1e-9):.4g} points/s), isosurface {t_iso:.3f}, '
-        f'colour query {t_col:.3f}, file write {t_write:.3f}')
+        f'colour query {t_col:.3f}, file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp))
   print(f'wrote {out}')
 
 
@@ -117,16 +156,18 @@ def main_tsdf(args, box, config, model, state, out, timed):
   frames = len(range(0, dataset.size, args.tsdf_stride))
   print(f'grid {tuple(volume.shape)}, spacing {volume.spacing:.6g}, truncation {volume.trunc:.6g}, {frames} frames of '
         f'{dataset.height} x {dataset.width} ({args.tsdf_split} split, {args.tsdf_depth})')
+  kept_faces = int(result['faces'].shape[0])
+  result, t_comp, t_simp = clean_up(args, result, volume.spacing, timed)
   os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
   _, t_write = timed(lambda: mesh.write_ply(out, result))
   stats = mesh.mesh_stats(result['vertices'], result['faces'])
-  print('mesh_stats: ' + ', '.join(f'{k} {v:.6g}' if isinstance(v, float) else f'{k} {v}' for k, v in stats.items()))
+  print('mesh_stats: ' + _format_stats(stats))
   unseen, total = int((volume.weight == 0).sum()), volume.weight.numel()
   print(f'never observed: {unseen} of {total} voxels ({unseen / total:.2%})')
   before = int(ops.marching_tetrahedra(volume.field()[0], 0., volume.origin, volume.spacing)[2].shape[0])
-  print(f'faces: {before} before the validity filter, {stats["T"]} after')
+  print(f'faces: {before} before the validity filter, {kept_faces} after')
   print(f'seconds: render {seconds["render"]:.3f}, fusion {seconds["fusion"]:.3f}, isosurface {seconds["isosurface"]:.3f}, '
-        f'file write {t_write:.3f}')
+        f'file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp))
   print(f'wrote {out}')
 
 

@@ -968,6 +968,103 @@ int mnr_tsdf_integrate(const mnr_tsdf_args* args, void* stream);
  * emit passes, mask bits of edges that leave the grid are ignored and nothing is written at or beyond keep[n_verts]. */
 int mnr_mt_vertex_valid(const mnr_mt_args* args, const unsigned char* valid, unsigned char* keep, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Mesh clean-up: connected components  (csrc/meshclean.hip)
+ * faces [n_faces,3] int32 over vertices 0 .. n_verts - 1.  labels [n_verts] int32 converges to: labels[v] = the smallest vertex
+ * id that v is connected to through face edges; a vertex in no face keeps its own id.  That result is unique, integer only
+ * (atomicMin, no floating point), so two runs agree bit for bit however the atomics interleave.
+ *   mnr_mesh_cc_init   labels[v] = v.
+ *   mnr_mesh_cc_sweep  one round of hooking (per face: the smallest of its three labels m is min-ed into every vertex x of the
+ *                      face whose label l is above m, and into labels[l]) and pointer jumping (per vertex: follow
+ *                      l = labels[l] while it decreases, store the end).  Adds nothing to *changed (an int on the device) when
+ *                      the hooking found every face with one label, stores 1 to it otherwise; it never stores 0.
+ * The caller zeroes a flag, runs sweeps and reads the flag back: the sweep that leaves its flag 0 has changed nothing and
+ * labels is the result (ops.mesh_components gives each sweep of a batch its own flag and reads a batch back at once).  A
+ * fixed iteration count is not a stopping rule: a label may have to travel the diameter of the mesh.  An index in faces
+ * outside [0, n_verts) makes its face be skipped, and every label is checked against [0, n_verts) before it is used as an
+ * index: no access leaves labels whatever faces and labels hold.  n_verts == 0 or n_faces == 0: nothing is launched by a sweep.
+ * ------------------------------------------------------------------------- */
+int mnr_mesh_cc_init(int64_t n_verts, int* labels, void* stream);
+int mnr_mesh_cc_sweep(const int* faces, int64_t n_faces, int64_t n_verts, int* labels, int* changed, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Mesh clean-up: simplification by vertex clustering with quadric-error placement  (csrc/meshclean.hip)
+ * (Lindstrom 2000, DeCoro-Tatarchuk 2007.)  One output vertex per occupied cell of a grid of cubes of side `cell` (float32,
+ * positive, finite) at `origin` (3 finite float32, HOST pointers below).  No atomics and no contraction anywhere: a cluster's
+ * sums belong to one thread, which adds in the order stated, so two runs agree bit for bit and a float64 restatement in the
+ * same order (tests/mesh_clean_ref.py) can differ in the last float32 rounding only.
+ *
+ * 1. Keys (mnr_mesh_cluster_keys), per vertex v and axis a, float32 in this order: q_a = floor((x_a - origin_a) / cell),
+ *    c_a = int(q_a).  keys[v] = (c_0 << 42) | (c_1 << 21) | c_2 as int64; MNR_MESH_KEY_NONFINITE where a coordinate is not
+ *    finite, else MNR_MESH_KEY_OUTSIDE where some q_a is outside [0, MNR_MESH_CELL_LIMIT).  The caller refuses a mesh with a
+ *    negative key.
+ * 2. The caller: the distinct keys in ascending order are the clusters, output vertex k is the k-th of them, map[v] is the rank
+ *    of keys[v]; members = the vertex ids stably sorted by map (a cluster's members in ascending id), member_start
+ *    [n_clusters + 1] their offsets.
+ * 3. Faces (mnr_mesh_cluster_faces), per face f = (a, b, c): mapped[f] = (map[a], map[b], map[c]); canon[f] = mapped[f] rotated
+ *    so that its smallest entry comes first (the first of equal ones); keep[f] = 1 iff the three clusters are distinct;
+ *    incident[f] = (map[a]; map[b] or -1 if it equals map[a]; map[c] or -1 if it equals map[a] or map[b]): each cluster the
+ *    face touches, once.  A face with an index outside [0, n_verts), or a map entry outside [0, n_clusters), gets -1
+ *    everywhere and keep 0.
+ * 4. The caller: cluster_faces = the face ids of the incident entries != -1, stably sorted by cluster from face-major order (a
+ *    cluster's faces in ascending id, each once), face_start [n_clusters + 1] their offsets, n_incident their number.  The
+ *    output faces are mapped[f] for the f with keep[f] = 1 that are the lowest id among the faces with the same canon[f], in
+ *    ascending f: order and winding survive, and of two faces that are the same directed triple up to rotation the first
+ *    stays.  Two coincident faces of OPPOSITE winding both stay.
+ * 5. Clusters (mnr_mesh_cluster_solve), one thread per cluster k, float64 throughout, inputs widened from float32:
+ *    m_a = origin_a + cell (c_a + 0.5) is the cell's centre (c_a from keys[k]); every coordinate below is relative to it,
+ *    p = double(vertex) - m.
+ *    members v in list order:  sg += p_v,  sn += normal_v,  sc += colour_v (integers),  count += 1.
+ *    g = sg / count.
+ *    faces f = (a, b, c) in list order:  e1 = p_b - p_a, e2 = p_c - p_a,
+ *      n = (e1_1 e2_2 - e1_2 e2_1, e1_2 e2_0 - e1_0 e2_2, e1_0 e2_1 - e1_1 e2_0),  L = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2);
+ *      the face is skipped unless 0 < L < inf;  d = (n_0 p_a0 + n_1 p_a1) + n_2 p_a2;
+ *      A_ij += (n_i n_j) / L for ij = 00, 01, 02, 11, 12, 22;  r_i += (n_i d) / L.
+ *      (E(x) = sum L (n/L . (x - p_a))^2, area-weighted, is x^T A x - 2 r^T x + const.)
+ *    tr = (A_00 + A_11) + A_22;  lam = (MNR_QEM_REG tr) / 3;  M = A + lam I;  b_i = r_i + lam g_i.
+ *    Closed-form solve by COFACTORS (adjugate over determinant):
+ *      c00 = M11 M22 - M12 M12, c01 = M02 M12 - M01 M22, c02 = M01 M12 - M02 M11,
+ *      c11 = M00 M22 - M02 M02, c12 = M01 M02 - M00 M12, c22 = M00 M11 - M01 M01,
+ *      det = (M00 c00 + M01 c01) + M02 c02,
+ *      x_0 = ((c00 b_0 + c01 b_1) + c02 b_2) / det, x_1 = ((c01 b_0 + c11 b_1) + c12 b_2) / det,
+ *      x_2 = ((c02 b_0 + c12 b_1) + c22 b_2) / det.
+ *    x is taken iff tr > 0, x is finite and |x_a| <= cell / 2 on every axis; otherwise x = g (fallback[k] = 1).
+ *    out_verts[k] = float32(m + x).  out_normals[k] = float32(sn / len), len = sqrt((sn_0 sn_0 + sn_1 sn_1) + sn_2 sn_2), or 0
+ *    unless 0 < len < inf.  out_colors[k] = (2 sc + count) / (2 count) in integers (the mean, halves rounded up).
+ *    MNR_QEM_REG is a decision, not a derived number: lam bounds the condition number of M by about 3 / MNR_QEM_REG, and where
+ *    the surface is flat (A of rank 1 or 2) it pulls the solution toward the centroid instead of letting it slide along
+ *    the plane.  The minimiser of E + lam |x - g|^2 cannot have a larger E than g, and the fallback is g: E(x) <= E(g).
+ *    Entries of members / cluster_faces / faces outside their ranges are skipped and the offsets are clipped to their lists: no
+ *    access leaves the inputs or row k of the outputs.
+ * n_verts == 0, n_faces == 0, n_clusters == 0 are successful no-ops of the entries they size.
+ * ------------------------------------------------------------------------- */
+#define MNR_QEM_REG 1e-3
+#define MNR_MESH_CELL_LIMIT (1 << 21)
+#define MNR_MESH_KEY_NONFINITE (-1)
+#define MNR_MESH_KEY_OUTSIDE (-2)
+typedef struct {
+  int64_t n_clusters, n_verts, n_faces, n_incident;
+  const float* verts;              /* [n_verts,3] */
+  const float* normals;            /* [n_verts,3] */
+  const unsigned char* colors;     /* [n_verts,3] or NULL */
+  const int* faces;                /* [n_faces,3] */
+  const int64_t* keys;             /* [n_clusters]: the distinct keys, ascending */
+  const int64_t* member_start;     /* [n_clusters + 1] */
+  const int* members;              /* [n_verts] */
+  const int64_t* face_start;       /* [n_clusters + 1] */
+  const int* cluster_faces;        /* [n_incident] */
+  float origin[3];
+  float cell;
+  float* out_verts;                /* [n_clusters,3] */
+  float* out_normals;              /* [n_clusters,3] */
+  unsigned char* out_colors;       /* [n_clusters,3] or NULL (colors and out_colors: both or neither) */
+  unsigned char* fallback;         /* [n_clusters] or NULL */
+} mnr_mesh_cluster_args;
+int mnr_mesh_cluster_keys(const float* verts, int64_t n_verts, const float* origin, float cell, int64_t* keys, void* stream);
+int mnr_mesh_cluster_faces(const int* faces, int64_t n_faces, const int* map, int64_t n_verts, int64_t n_clusters, int* mapped,
+                           int* canon, int* incident, unsigned char* keep, void* stream);
+int mnr_mesh_cluster_solve(const mnr_mesh_cluster_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

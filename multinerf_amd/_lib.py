@@ -218,6 +218,18 @@ class TsdfArgs(C.Structure):
               ('rgb', vp), ('tsdf', vp), ('weight', vp), ('color', vp)]
 
 
+QEM_REG = 1e-3                     # MNR_QEM_REG
+MESH_CELL_LIMIT = 1 << 21          # MNR_MESH_CELL_LIMIT
+MESH_KEY_NONFINITE, MESH_KEY_OUTSIDE = -1, -2
+
+
+class MeshClusterArgs(C.Structure):
+  _fields_ = [('n_clusters', C.c_int64), ('n_verts', C.c_int64), ('n_faces', C.c_int64), ('n_incident', C.c_int64), ('verts', vp),
+              ('normals', vp), ('colors', vp), ('faces', vp), ('keys', vp), ('member_start', vp), ('members', vp), ('face_start', vp),
+              ('cluster_faces', vp), ('origin', C.c_float * 3), ('cell', C.c_float), ('out_verts', vp), ('out_normals', vp),
+              ('out_colors', vp), ('fallback', vp)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('one_minus_b1', C.c_float),
@@ -313,6 +325,11 @@ _PROTOS = {
     'mnr_mt_emit_faces': ([C.POINTER(MtArgs), vp], i32),
     'mnr_tsdf_integrate': ([C.POINTER(TsdfArgs), vp], i32),
     'mnr_mt_vertex_valid': ([C.POINTER(MtArgs), vp, vp, vp], i32),
+    'mnr_mesh_cc_init': ([i64, vp, vp], i32),
+    'mnr_mesh_cc_sweep': ([vp, i64, i64, vp, vp, vp], i32),
+    'mnr_mesh_cluster_keys': ([vp, i64, C.POINTER(f32), f32, vp, vp], i32),
+    'mnr_mesh_cluster_faces': ([vp, i64, vp, i64, i64, vp, vp, vp, vp, vp], i32),
+    'mnr_mesh_cluster_solve': ([C.POINTER(MeshClusterArgs), vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

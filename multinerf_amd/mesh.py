@@ -7,6 +7,8 @@
   tsdf_mesh      render the cameras of a dataset and fuse their depth into a TsdfVolume
   write_ply / read_ply   binary_little_endian 1.0
   mesh_stats     counts, Euler characteristic, open and non-manifold edges, signed volume, area (host, float64)
+  filter_components / component_stats   connected components (ops.mesh_components, csrc/meshclean.hip): drop the small ones
+  simplify       vertex clustering on a coarser grid with quadric-error placement (csrc/meshclean.hip)
 
 Grid convention (the kernels' own): field[i, j, k] sits at origin + spacing * (i, j, k), the linear point index is
 (i * ny + j) * nz + k, and a point is inside iff field >= level.
@@ -18,6 +20,7 @@ import time
 import numpy as np
 import torch
 
+from multinerf_amd import _lib as L
 from multinerf_amd import camera_utils, models, ops
 
 # samples of one `mlp_call`: it keeps features, tangent rows and every layer's activations.  Measured for the 360 preset at
@@ -266,6 +269,137 @@ def tsdf_mesh(model, params, dataset, config, bbox_min, bbox_max, resolution, tr
   if timings is not None:
     timings.update(seconds)
   return result, volume
+
+
+def _compact(m, keep_faces):
+  """The mesh dict restricted to the faces of a bool mask: vertices no kept face refers to are removed, the faces re-indexed,
+  the order of the surviving vertices and faces unchanged."""
+  verts, faces = m['vertices'], m['faces']
+  V = int(verts.shape[0])
+  faces = faces[keep_faces]
+  used = torch.zeros((V,), dtype=torch.bool, device=verts.device)
+  used[faces.reshape(-1).long()] = True
+  new_id = (torch.cumsum(used, 0, dtype=torch.int64) - 1).to(torch.int32)
+  colors = m.get('colors')
+  return dict(vertices=verts[used].contiguous(), normals=m['normals'][used].contiguous(),
+              faces=new_id[faces.long()].reshape(-1, 3).contiguous(), colors=None if colors is None else colors[used].contiguous())
+
+
+def _component_counts(m):
+  """(labels [V] int32, faces per label [V] int64, vertices per label [V] int64) on the device."""
+  V = int(m['vertices'].shape[0])
+  faces = m['faces'].contiguous()
+  labels = ops.mesh_components(faces, V)
+
+  def count(ids):                                           # a sort, not torch.bincount: its atomics pile up on one bin where
+    out = torch.zeros((V,), dtype=torch.int64, device=ids.device)                      # the mesh is one big component
+    which, n = torch.unique(ids.long(), return_counts=True)
+    out[which] = n
+    return out
+
+  return labels, count(labels[faces[:, 0].long()]), count(labels)
+
+
+def filter_components(m, min_faces=0, keep_largest=0, return_labels=False):
+  """The mesh dict without its small connected components.  A component (ops.mesh_components: vertices joined through face edges,
+  named by its smallest vertex id) is kept iff it has at least `min_faces` faces and, with keep_largest > 0, is among the
+  `keep_largest` components with the most faces (ties go to the smaller label).  The vertices of dropped components go, and so do
+  vertices no face refers to; surviving vertices and faces keep their order, faces are re-indexed, normals and colours are
+  carried along.  The criterion is a face COUNT (integers, exact); an area would need ordered float sums.
+  return_labels=True adds `labels` [V] int32, the INPUT mesh's component labels."""
+  min_faces, keep_largest = int(min_faces), int(keep_largest)
+  if min_faces < 0 or keep_largest < 0:
+    raise ValueError(f'filter_components: min_faces = {min_faces} and keep_largest = {keep_largest} must not be negative')
+  labels, n_faces, _ = _component_counts(m)
+  keep = (n_faces >= min_faces) & (n_faces > 0)
+  if keep_largest > 0:
+    order = torch.sort(n_faces, descending=True, stable=True).indices[:keep_largest]     # stable: equal counts in ascending label
+    top = torch.zeros_like(keep)
+    top[order] = True
+    keep &= top
+  out = _compact(m, keep[labels[m['faces'][:, 0].long()].long()])
+  if return_labels:
+    out['labels'] = labels
+  return out
+
+
+def component_stats(m):
+  """dict(count, faces=[...], vertices=[...]) of the mesh's connected components on the host: their number (a vertex in no face
+  is a component of its own, with 0 faces) and their face and vertex counts, ordered by descending face count, then label."""
+  labels, n_faces, n_verts = _component_counts(m)
+  ids = torch.nonzero(n_verts).reshape(-1)
+  f, v = n_faces[ids], n_verts[ids]
+  order = torch.sort(f, descending=True, stable=True).indices
+  return dict(count=int(ids.shape[0]), faces=f[order].tolist(), vertices=v[order].tolist())
+
+
+def simplify(m, cell, origin=None, return_map=False):
+  """Vertex clustering with quadric-error placement (Lindstrom 2000, DeCoro-Tatarchuk 2007): one output vertex per occupied cell
+  of a grid of cubes of side `cell` (world units, positive and finite) at `origin` (default: the per-axis minimum of the
+  vertices, one read-back).  include/mnerf.h states the contract: the cell of a vertex is int(floor((x - origin) / cell)) in
+  float32, clusters are ordered by (cx, cy, cz), a cluster's vertex minimises the area-weighted squared distance to the planes
+  of every face that touches the cluster, regularised toward the members' centroid and confined to the cell (the centroid where
+  the solve fails or leaves the cell), its normal is the normalised sum and its colour the rounded mean of the members'.  A
+  face survives iff its three clusters are distinct and no earlier face is the same directed triple up to rotation; surviving
+  faces keep their order and winding.  Returns a new mesh dict; return_map=True adds `map` [V] int32, vertex -> output vertex,
+  and `fallback` [V'] bool, the clusters placed at their centroid.
+
+  Limitations: vertex clustering does not preserve manifoldness (two sheets closer than a cell merge, an edge may end up with
+  more than two faces), and a pair of coincident faces of OPPOSITE winding (a thin sheet collapsed onto itself) stays in.
+  A vertex that is not finite, or a cell index outside [0, 2^21), raises ValueError.  The sorts, `unique`, scans and compaction
+  are torch on the device; the read-backs are the origin, the smallest key and the sizes."""
+  verts, normals, faces, colors = m['vertices'].contiguous(), m['normals'].contiguous(), m['faces'].contiguous(), m.get('colors')
+  colors = None if colors is None else colors.contiguous()
+  dev = verts.device
+  V, T = int(verts.shape[0]), int(faces.shape[0])
+  cell = float(np.float32(cell)) if math.isfinite(float(cell)) else float(cell)
+  if not (cell > 0. and math.isfinite(cell)):
+    raise ValueError(f'simplify: cell = {cell} must be positive and finite')
+  if V == 0:
+    out = dict(vertices=verts.clone(), normals=normals.clone(), faces=torch.zeros((0, 3), dtype=torch.int32, device=dev),
+               colors=None if colors is None else colors.clone())
+    if return_map:
+      out['map'], out['fallback'] = torch.zeros((0,), dtype=torch.int32, device=dev), torch.zeros((0,), dtype=torch.bool, device=dev)
+    return out
+  if origin is None:
+    origin = verts.min(0).values.tolist()
+    if not all(math.isfinite(v) for v in origin):
+      raise ValueError('simplify: a vertex is not finite')
+  origin = [float(np.float32(v)) for v in (origin.tolist() if torch.is_tensor(origin) else origin)]
+  keys = ops.mesh_cluster_keys(verts, origin, cell)
+  worst = int(keys.min())
+  if worst == L.MESH_KEY_NONFINITE:
+    raise ValueError('simplify: a vertex is not finite')
+  if worst == L.MESH_KEY_OUTSIDE:
+    lo = (verts.min(0).values.double() - torch.tensor(origin, dtype=torch.float64, device=dev)).min().item()
+    if lo < 0:
+      raise ValueError(f'simplify: a vertex lies {-lo:.6g} below the origin {origin}: every vertex must be at or above it')
+    extent = (verts.max(0).values.double() - torch.tensor(origin, dtype=torch.float64, device=dev)).max().item()
+    raise ValueError(f'simplify: cell = {cell:.6g} puts a vertex beyond cell index 2^21 - 1; the smallest legal cell for this mesh '
+                     f'and origin is {extent / (L.MESH_CELL_LIMIT - 1):.6g}')
+  ukeys, vmap = torch.unique(keys, sorted=True, return_inverse=True)
+  K = int(ukeys.shape[0])
+  members = torch.sort(vmap, stable=True).indices.to(torch.int32)
+  zero = torch.zeros((1,), dtype=torch.int64, device=dev)
+  member_start = torch.cat([zero, torch.cumsum(torch.bincount(vmap, minlength=K), 0)])
+  vmap = vmap.to(torch.int32)
+  mapped, canon, incident, keep = ops.mesh_cluster_faces(faces, vmap, K)
+  inc = incident.reshape(-1)                                 # face-major: a stable sort by cluster leaves face ids ascending
+  at = torch.nonzero(inc >= 0).reshape(-1)
+  inc = inc[at].long()
+  cluster_faces = (at[torch.sort(inc, stable=True).indices] // 3).to(torch.int32)
+  face_start = torch.cat([zero, torch.cumsum(torch.bincount(inc, minlength=K), 0)])
+  out_v, out_n, out_c, fallback = ops.mesh_cluster_solve(verts, normals, colors, faces, ukeys, member_start, members, face_start, cluster_faces,
+                                                  origin, cell)
+  ids = torch.nonzero(keep).reshape(-1)                      # distinct clusters; then the lowest id of every directed triple
+  if ids.shape[0] > 0:
+    _, group = torch.unique(canon[ids], dim=0, return_inverse=True)
+    first = torch.full((int(group.max()) + 1,), T, dtype=torch.int64, device=dev).scatter_reduce(0, group, ids, 'amin')
+    ids = ids[first[group] == ids]
+  out = dict(vertices=out_v, normals=out_n, faces=mapped[ids].contiguous(), colors=out_c)
+  if return_map:
+    out['map'], out['fallback'] = vmap, fallback != 0
+  return out
 
 
 def _host(x, dtype):

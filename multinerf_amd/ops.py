@@ -1680,3 +1680,121 @@ def tsdf_integrate(tsdf, weight, color, origin, spacing, trunc, proj, depth, acc
   a.proj, a.depth, a.acc, a.rgb = proj.data_ptr(), depth.data_ptr(), _ptr(acc), _ptr(rgb)
   a.tsdf, a.weight, a.color = tsdf.data_ptr(), weight.data_ptr(), _ptr(color)
   L.check(lib().mnr_tsdf_integrate(C.byref(a), _stream()))
+
+
+# ----------------------------------------------------------------------------- mesh clean-up (csrc/meshclean.hip)
+
+# sweeps between two read-backs of the convergence flags of `mesh_components`
+CC_SWEEPS_PER_READBACK = 4
+
+
+def _chk_faces(name, faces, n_verts):
+  _chk(faces, torch.int32, f'{name}: faces')
+  n_verts = int(n_verts)
+  if faces.dim() != 2 or faces.shape[1] != 3:
+    raise ValueError(f'{name}: faces must be [T,3], is {tuple(faces.shape)}')
+  if not 0 <= n_verts < 2 ** 31 or faces.shape[0] >= 2 ** 31:
+    raise ValueError(f'{name}: {n_verts} vertices and {faces.shape[0]} faces: both must lie in 0 .. 2^31 - 1')
+  if faces.shape[0] > 0:
+    lo, hi = int(faces.min()), int(faces.max())
+    if lo < 0 or hi >= n_verts:
+      raise ValueError(f'{name}: faces holds indices {lo} .. {hi}, outside the {n_verts} vertices')
+  return n_verts, int(faces.shape[0])
+
+
+def mesh_components(faces, n_verts, return_sweeps=False):
+  """labels [n_verts] int32 of an indexed triangle mesh (mnr_mesh_cc_init / mnr_mesh_cc_sweep): labels[v] is the smallest vertex
+  id v is connected to through face edges, a vertex in no face is its own label.  faces [T,3] int32 on the device; an index
+  outside [0, n_verts) raises ValueError (one min / max read-back).  The sweeps run until one of them changes nothing: each
+  sweep of a batch of CC_SWEEPS_PER_READBACK has a device flag of its own, and the batch's flags are read back together (the
+  loop's one synchronisation per batch); there is no iteration limit.  Integer min only: two runs agree bit for bit.
+  return_sweeps=True appends the number of sweeps up to and including the one that changed nothing."""
+  V, T = _chk_faces('mesh_components', faces, n_verts)
+  labels = torch.empty((V,), dtype=torch.int32, device=faces.device)
+  L.check(lib().mnr_mesh_cc_init(V, _ptr(labels), _stream()))
+  sweeps = 0
+  while V > 0 and T > 0:
+    flags = torch.zeros((CC_SWEEPS_PER_READBACK,), dtype=torch.int32, device=faces.device)
+    for n in range(CC_SWEEPS_PER_READBACK):
+      L.check(lib().mnr_mesh_cc_sweep(_ptr(faces), T, V, _ptr(labels), C.c_void_p(flags.data_ptr() + 4 * n), _stream()))
+    flags = flags.tolist()
+    if 0 in flags:
+      sweeps += flags.index(0) + 1
+      break
+    sweeps += CC_SWEEPS_PER_READBACK
+  return (labels, sweeps) if return_sweeps else labels
+
+
+def _chk_cell(name, origin, cell):
+  cell = C.c_float(float(cell)).value                        # what the kernels see
+  if not (cell > 0. and math.isfinite(cell)):
+    raise ValueError(f'{name}: cell must be positive and finite in float32, is {cell}')
+  origin = [float(v) for v in (origin.tolist() if torch.is_tensor(origin) else origin)]
+  if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
+    raise ValueError(f'{name}: origin must hold 3 finite values, is {origin}')
+  return (C.c_float * 3)(*origin), cell
+
+
+def mesh_cluster_keys(verts, origin, cell):
+  """keys [V] int64 of the vertices' cells (mnr_mesh_cluster_keys; include/mnerf.h): (cx << 42) | (cy << 21) | cz with
+  c = int(floor((x - origin) / cell)) in float32, _lib.MESH_KEY_NONFINITE for a vertex that is not finite, _lib.MESH_KEY_OUTSIDE
+  for an index outside [0, 2^21).  No read-back: the caller looks at the smallest key."""
+  _chk(verts, f32, 'mesh_cluster_keys: verts')
+  if verts.dim() != 2 or verts.shape[1] != 3:
+    raise ValueError(f'mesh_cluster_keys: verts must be [V,3], is {tuple(verts.shape)}')
+  o, cell = _chk_cell('mesh_cluster_keys', origin, cell)
+  keys = torch.empty((verts.shape[0],), dtype=torch.int64, device=verts.device)
+  L.check(lib().mnr_mesh_cluster_keys(_ptr(verts), int(verts.shape[0]), o, cell, _ptr(keys), _stream()))
+  return keys
+
+
+def mesh_cluster_faces(faces, vmap, n_clusters):
+  """(mapped [T,3] int32, canon [T,3] int32, incident [T,3] int32, keep [T] uint8) of the faces under the vertex -> cluster map
+  `vmap` [V] int32 (mnr_mesh_cluster_faces): the re-indexed face, the same rotated so that its smallest cluster comes first, each
+  cluster the face touches once (-1 in the other slots), and whether its three clusters are distinct."""
+  name = 'mesh_cluster_faces'
+  _chk(faces, torch.int32, f'{name}: faces')
+  _chk(vmap, torch.int32, f'{name}: vmap')
+  if faces.dim() != 2 or faces.shape[1] != 3 or vmap.dim() != 1:
+    raise ValueError(f'{name}: faces must be [T,3] and vmap [V], are {tuple(faces.shape)} and {tuple(vmap.shape)}')
+  T, dev = int(faces.shape[0]), faces.device
+  mapped, canon, incident = (torch.empty((T, 3), dtype=torch.int32, device=dev) for _ in range(3))
+  keep = torch.empty((T,), dtype=torch.uint8, device=dev)
+  L.check(lib().mnr_mesh_cluster_faces(_ptr(faces), T, _ptr(vmap), int(vmap.shape[0]), int(n_clusters), _ptr(mapped), _ptr(canon),
+                                       _ptr(incident), _ptr(keep), _stream()))
+  return mapped, canon, incident, keep
+
+
+def mesh_cluster_solve(verts, normals, colors, faces, keys, member_start, members, face_start, cluster_faces, origin, cell):
+  """(out_verts [K,3] float32, out_normals [K,3] float32, out_colors [K,3] uint8 or None, fallback [K] uint8) of the K clusters
+  (mnr_mesh_cluster_solve; include/mnerf.h states the sums, their order and the closed-form solve): keys [K] int64 the distinct
+  cell keys ascending, members [V] int32 with offsets member_start [K+1] int64, cluster_faces [n] int32 with offsets face_start
+  [K+1] int64, colors [V,3] uint8 or None.  fallback marks the clusters placed at their centroid."""
+  name = 'mesh_cluster_solve'
+  for t, dt, label in ((verts, f32, 'verts'), (normals, f32, 'normals'), (faces, torch.int32, 'faces'), (keys, torch.int64, 'keys'),
+                       (member_start, torch.int64, 'member_start'), (members, torch.int32, 'members'),
+                       (face_start, torch.int64, 'face_start'), (cluster_faces, torch.int32, 'cluster_faces')):
+    _chk(t, dt, f'{name}: {label}')
+  _chk(colors, torch.uint8, f'{name}: colors', allow_none=True)
+  V, T, K = int(verts.shape[0]), int(faces.shape[0]), int(keys.shape[0])
+  if tuple(verts.shape) != (V, 3) or normals.shape != verts.shape or tuple(faces.shape) != (T, 3) or \
+      (colors is not None and colors.shape != verts.shape):
+    raise ValueError(f'{name}: verts, normals and colors must be [V,3] and faces [T,3]')
+  if tuple(member_start.shape) != (K + 1,) or tuple(face_start.shape) != (K + 1,) or tuple(members.shape) != (V,) or cluster_faces.dim() != 1:
+    raise ValueError(f'{name}: member_start and face_start must be [K+1], members [V] and cluster_faces a list')
+  o, cell = _chk_cell(name, origin, cell)
+  dev = verts.device
+  out_v = torch.empty((K, 3), dtype=f32, device=dev)
+  out_n = torch.empty((K, 3), dtype=f32, device=dev)
+  out_c = None if colors is None else torch.empty((K, 3), dtype=torch.uint8, device=dev)
+  fallback = torch.empty((K,), dtype=torch.uint8, device=dev)
+  a = L.MeshClusterArgs()
+  a.n_clusters, a.n_verts, a.n_faces, a.n_incident = K, V, T, int(cluster_faces.shape[0])
+  a.verts, a.normals, a.colors, a.faces = verts.data_ptr(), normals.data_ptr(), _ptr(colors), faces.data_ptr()
+  a.keys, a.member_start, a.members = keys.data_ptr(), member_start.data_ptr(), members.data_ptr()
+  a.face_start, a.cluster_faces = face_start.data_ptr(), cluster_faces.data_ptr()
+  a.origin[0], a.origin[1], a.origin[2] = o
+  a.cell = cell
+  a.out_verts, a.out_normals, a.out_colors, a.fallback = out_v.data_ptr(), out_n.data_ptr(), _ptr(out_c), fallback.data_ptr()
+  L.check(lib().mnr_mesh_cluster_solve(C.byref(a), _stream()))
+  return out_v, out_n, out_c, fallback

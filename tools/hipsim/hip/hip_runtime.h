@@ -200,6 +200,11 @@ inline unsigned atomicAdd(unsigned* p, unsigned v) {
   *p = o + v;
   return o;
 }
+inline int atomicMin(int* p, int v) {
+  const int o = *p;
+  *p = v < o ? v : o;
+  return o;
+}
 inline float __shfl(float v, int src, int width = 64) { return hipsim::shfl(v, src, width); }
 inline float __shfl_down(float v, unsigned d, int width = 64) {
   const int l = hipsim::cur->lane;
