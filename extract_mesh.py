@@ -18,6 +18,13 @@ shells of their own) and --simplify F merges the vertices of every cube of F gri
 error of the faces around it (`mesh.simplify`, csrc/meshclean.hip); components first, then simplification, with either method.
 With all three at their defaults nothing of this runs and the file is the one written before.
 
+--texture C bakes a texture atlas after the clean-up (`mesh.bake_texture`, csrc/atlas.hip): every face gets a chart of C texels a
+side, every texel is coloured by the NeRF MLP at the Gaussian of its own footprint (--texture_filter texels wide), and the file
+carries per-face texture coordinates next to <out>.png; --out x.obj writes OBJ + MTL + PNG instead of PLY.  So
+--simplify 4 --texture 8 gives a mesh about 16 times lighter with more colour samples per area than the vertex-coloured original.
+With --method tsdf the texture comes from the MLP as well; the vertex colours stay the fused ones.  An atlas with a side above
+--texture_max_side is refused before anything is baked.
+
   python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
       --resolution 512 --density_threshold 10 --out garden.ply
   python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
@@ -25,13 +32,14 @@ With all three at their defaults nothing of this runs and the file is the one wr
 """
 
 import argparse
+import math
 import os
 import sys
 import time
 
 import torch
 
-from multinerf_amd import checkpoints, configs, mesh, ops, train_utils
+from multinerf_amd import _lib, checkpoints, configs, mesh, ops, train_utils
 
 
 def parse_args(argv):
@@ -58,6 +66,10 @@ def parse_args(argv):
   ap.add_argument('--min_component_faces', type=int, default=0, help='drop connected components with fewer faces (0: keep all)')
   ap.add_argument('--keep_largest', type=int, default=0, help='keep only this many components with the most faces (0: keep all)')
   ap.add_argument('--simplify', type=float, default=0., help='vertex clustering with a cell of this many grid spacings (0: off)')
+  ap.add_argument('--texture', type=int, default=0, help='bake a texture atlas with face charts of this many texels a side (0: off; else >= 3)')
+  ap.add_argument('--texture_filter', type=float, default=1.0, help="width of a texel's query Gaussian in texels (0: point samples)")
+  ap.add_argument('--texture_max_side', type=int, default=16384,
+                  help='refuse an atlas with a longer side (a decision: 16384 is the common hardware texture limit)')
   # `--bbox -1,-1,-1,1,1,1`: argparse takes a value that starts with '-' and is no plain number for an option; hand it over as --bbox=...
   argv = list(argv)
   for i in range(len(argv) - 1):
@@ -73,6 +85,10 @@ def parse_args(argv):
     raise SystemExit(f'extract_mesh.py: --bbox {args.bbox!r} must be six numbers x0,y0,z0,x1,y1,z1') from None
   if args.min_component_faces < 0 or args.keep_largest < 0 or not (0. <= args.simplify < float('inf')):
     raise SystemExit('extract_mesh.py: --min_component_faces, --keep_largest and --simplify must not be negative')
+  if args.texture != 0 and args.texture < _lib.ATLAS_MIN_CELL:
+    raise SystemExit(f'extract_mesh.py: --texture must be 0 (off) or at least {_lib.ATLAS_MIN_CELL}')
+  if not (0. <= args.texture_filter < float('inf')) or args.texture_max_side < 1:
+    raise SystemExit('extract_mesh.py: --texture_filter must be finite and not negative, --texture_max_side positive')
   return args, box
 
 
@@ -101,6 +117,38 @@ def clean_up(args, result, spacing, timed):
     result, t_simp = timed(lambda: mesh.simplify(result, args.simplify * spacing))
   report('after clean-up', result)
   return result, t_comp, t_simp
+
+
+def bake_and_write(args, model, result, out, timed):
+  """Write `result` to `out` (OBJ for an .obj name, else PLY), with a texture atlas baked from the model's NeRF MLP when --texture is
+  set; returns (seconds of the bake, seconds of the file write).  An atlas beyond --texture_max_side stops the script before the
+  bake and names the --simplify factor that would fit."""
+  texture, t_bake = None, 0.
+  n_faces = int(result['faces'].shape[0])
+  if args.texture > 0 and n_faces > 0:
+    layout = ops.atlas_layout(n_faces, args.texture)
+    side = max(layout['W'], layout['H'])
+    if side > args.texture_max_side:
+      # the face count falls with the square of the clustering cell, the atlas side with the root of the face count
+      factor = math.ceil((args.simplify if args.simplify > 0. else 1.) * side / args.texture_max_side * 10.) / 10.
+      raise SystemExit(f'extract_mesh.py: the atlas of {n_faces} faces at --texture {args.texture} is {layout["W"]} x {layout["H"]} texels, beyond '
+                       f'--texture_max_side {args.texture_max_side}; about --simplify {factor:.1f} would fit')
+    print(f'texture: {layout["W"]} x {layout["H"]}, {layout["n_samples"]} samples, cell {args.texture}')
+    texture, t_bake = timed(lambda: mesh.bake_texture(result, model=model, cell=args.texture, filter=args.texture_filter, chunk=args.chunk))
+  elif args.texture > 0:
+    print('texture: the mesh has no faces, nothing to bake')
+  os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+  if out.lower().endswith('.obj'):
+    if texture is None:
+      raise SystemExit('extract_mesh.py: --out x.obj needs --texture (and a mesh with faces): the OBJ writer writes textured meshes')
+    _, t_write = timed(lambda: mesh.write_obj(out, result, texture))
+  else:
+    _, t_write = timed(lambda: mesh.write_ply(out, result, texture=texture))
+  return t_bake, t_write
+
+
+def _texture_seconds(args, t_bake):
+  return f', texture bake {t_bake:.3f}' if args.texture > 0 else ''
 
 
 def main():
@@ -137,12 +185,11 @@ def main():
   result = dict(vertices=verts, normals=normals, faces=faces, colors=colors)
   result, t_comp, t_simp = clean_up(args, result, spacing, timed)
   verts, faces = result['vertices'], result['faces']
-  os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-  _, t_write = timed(lambda: mesh.write_ply(out, result))
+  t_bake, t_write = bake_and_write(args, model, result, out, timed)
   stats = mesh.mesh_stats(verts, faces)
   print('mesh_stats: ' + _format_stats(stats))
   print(f'seconds: grid query {t_grid:.3f} ({field.numel() / max(t_grid, 1e-9):.4g} points/s), isosurface {t_iso:.3f}, '
-        f'colour query {t_col:.3f}, file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp))
+        f'colour query {t_col:.3f}, file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp) + _texture_seconds(args, t_bake))
   print(f'wrote {out}')
 
 
@@ -158,8 +205,7 @@ def main_tsdf(args, box, config, model, state, out, timed):
         f'{dataset.height} x {dataset.width} ({args.tsdf_split} split, {args.tsdf_depth})')
   kept_faces = int(result['faces'].shape[0])
   result, t_comp, t_simp = clean_up(args, result, volume.spacing, timed)
-  os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-  _, t_write = timed(lambda: mesh.write_ply(out, result))
+  t_bake, t_write = bake_and_write(args, model, result, out, timed)
   stats = mesh.mesh_stats(result['vertices'], result['faces'])
   print('mesh_stats: ' + _format_stats(stats))
   unseen, total = int((volume.weight == 0).sum()), volume.weight.numel()
@@ -167,7 +213,7 @@ def main_tsdf(args, box, config, model, state, out, timed):
   before = int(ops.marching_tetrahedra(volume.field()[0], 0., volume.origin, volume.spacing)[2].shape[0])
   print(f'faces: {before} before the validity filter, {kept_faces} after')
   print(f'seconds: render {seconds["render"]:.3f}, fusion {seconds["fusion"]:.3f}, isosurface {seconds["isosurface"]:.3f}, '
-        f'file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp))
+        f'file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp) + _texture_seconds(args, t_bake))
   print(f'wrote {out}')
 
 

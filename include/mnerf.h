@@ -1065,6 +1065,78 @@ int mnr_mesh_cluster_faces(const int* faces, int64_t n_faces, const int* map, in
                            int* canon, int* incident, unsigned char* keep, void* stream);
 int mnr_mesh_cluster_solve(const mnr_mesh_cluster_args* args, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Texture atlas: per-face charts in a regular grid of cells  (csrc/atlas.hip)
+ * A closed-form layout: no chart growing, no packing, no hashing, no atomics, no contraction.  Two runs write the same atlas and
+ * a NumPy restatement (tests/atlas_ref.py) follows it exactly.  T = n_faces, c >= MNR_ATLAS_MIN_CELL the cell size in texels.
+ *
+ * Layout.  Faces 2k and 2k + 1 share cell k; ncells = ceil(T / 2).  A cell is (c + 1) texels wide and c high; cells fill the atlas
+ * row-major, `cols` per row: W = cols (c + 1), rows = ceil(ncells / cols), H = rows c (T = 0: W = H = 0).  Row 0 is the TOP row of
+ * the image.  The top-left texel of cell k is (X0, Y0) = ((k % cols) (c + 1), (k / cols) c).
+ *
+ * Ownership.  The local texel (X, Y), X in 0 .. c, Y in 0 .. c - 1, belongs to the lower face 2k iff X + Y <= c - 1 and to the upper
+ * face 2k + 1 otherwise: c (c + 1) / 2 texels each, every texel of a cell has exactly one owner.  The upper half is the lower half
+ * rotated by 180 degrees about the cell's centre.  In FACE-LOCAL texels (x', y'), x', y' >= 0, x' + y' <= c - 1:
+ *   lower  (x', y') = (X, Y)                    i.e. texel (X0 + x', Y0 + y')
+ *   upper  (x', y') = (c - X, c - 1 - Y)        i.e. texel (X0 + c - x', Y0 + c - 1 - y')
+ * so a face's chart is one anchor texel (its v0) and a step of +1 (lower) or -1 (upper) along both axes.
+ *
+ * Texel to surface (mnr_atlas_samples), float32 in the order written:
+ *   b1 = float(x') / float(c - 2),  b2 = float(y') / float(c - 2),  b0 = (1 - b1) - b2,  p = (b0 v0 + b1 v1) + b2 v2.
+ * v0 is the texel x' = y' = 0, v1 the texel x' = c - 2, v2 the texel y' = c - 2.  The texels with x' + y' = c - 1 (and so those with
+ * x' = c - 1 or y' = c - 1) lie just outside the triangle, b0 < 0: they are the GUTTER, baked at the extrapolated point of the
+ * face's plane and not dilated afterwards.
+ *
+ * Surface to UV (mnr_atlas_uvs).  Texel centres are at + 0.5; the pixel position of the barycentric point (b0, b1, b2) is the centre
+ * of the anchor texel plus or minus (c - 2) (b1, b2).  With x' = c - 2 for v1 and y' = c - 2 for v2 in the two rows above:
+ *          v0                         v1                           v2
+ *   lower  (X0 + .5,     Y0 + .5)     (X0 + c - 1.5, Y0 + .5)      (X0 + .5,     Y0 + c - 1.5)      = X0 + x' + .5, Y0 + y' + .5
+ *   upper  (X0 + c + .5, Y0 + c - .5) (X0 + 2.5,     Y0 + c - .5)  (X0 + c + .5, Y0 + 1.5)          = X0 + c - x' + .5, Y0 + c - 1 - y' + .5
+ *   u = px / float(W),  v = 1 - py / float(H)   (float32; v = 1 is the top of the image).
+ * The UV triangle is the owned region shrunk by one texel from the hypotenuse, which makes the texture seam-safe WITHOUT padding:
+ * a bilinear lookup at s = (c - 2) b1, t = (c - 2) b2 (s, t >= 0, s + t <= c - 2) reads the face-local texels (i, j), (i + 1, j),
+ * (i, j + 1), (i + 1, j + 1) with i = floor(s), j = floor(t).  i + j <= c - 2, so the first three have x' + y' <= c - 1: owned.  The
+ * fourth is not owned only if i + j = c - 2, which needs s + t = c - 2 with s = i and t = j: both fractions are 0 and its weight
+ * is exactly 0.  (In exact arithmetic: a UV rounded to float32 is off by up to 2^-24 of itself, a weight of that order.)
+ *
+ * Footprint.  A texel is the parallelogram spanned by a = (v1 - v0) / float(c - 2) and b = (v2 - v0) / float(c - 2) (float32).  The
+ * Gaussian with the moments of the uniform distribution over it, scaled by the filter width, has mean p and
+ *   cov_ij = cov_scale (a_i a_j + b_i b_j),  cov_scale = filter^2 / 12 (float64 on the host, passed as a float; 0: point samples).
+ * The covariance has rank 2: flat along the normal.  mnr_ipe_from_gaussians takes it as it is.
+ *
+ * Normal and view direction.  n = (b0 n0 + b1 n1) + b2 n2 over len = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2) where 0 < len < inf; else
+ * the face normal g = (v1 - v0) x (v2 - v0), g_0 = e1_1 e2_2 - e1_2 e2_1 and cyclic, over its length under the same condition;
+ * else (0, 0, 1).  viewdir = -n; with the last fallback the view direction is (0, 0, 1) too.
+ *
+ * Invalid samples: the upper half of the last cell when T is odd; a face with a vertex position that is not finite (or an index
+ * outside [0, n_verts)); a sample whose mean or covariance is not finite in float32.  They get zero mean and covariance, normal
+ * and view direction (0, 0, 1) and face = -1; mnr_atlas_store skips them, so their texels keep what the caller put there and the
+ * mask stays as it was.  Every output is finite.
+ *
+ * Samples are numbered s = cell c (c + 1) + Y (c + 1) + X, the total is ncells c (c + 1) (int64).  A chunk [s0, s0 + n) is any range
+ * of them, n < 2^31: memory is bounded by the chunk, not by the atlas.
+ *   mnr_atlas_samples  one thread per sample: means [n,3], covs [n,3,3], normals [n,3], viewdirs [n,3], face [n] (76 B a sample).
+ *   mnr_atlas_store    per sample with face >= 0: atlas[Y0 + Y, X0 + X] = floor(clip(rgb, 0, 1) * 255 + 0.5) (NaN counts as 0),
+ *                      mask = 255 there, and atlas_f32 (when given) the rgb as it came.  One sample per texel: no atomics.
+ *   mnr_atlas_uvs      uv [T,3,2]: (u, v) of v0, v1, v2 of every face.  Reads only c, cols, W, H and n_faces.
+ * ------------------------------------------------------------------------- */
+#define MNR_ATLAS_MIN_CELL 3
+typedef struct {
+  const float* verts;              /* [n_verts,3] */
+  const float* normals;            /* [n_verts,3] */
+  const int* faces;                /* [n_faces,3] */
+  int64_t n_verts, n_faces;
+  int c;                           /* cell size in texels, >= MNR_ATLAS_MIN_CELL */
+  int cols;                        /* cells per atlas row, >= 1 */
+  int W, H;                        /* cols (c + 1) and ceil(ceil(n_faces / 2) / cols) c; both 0 when n_faces == 0 */
+  float cov_scale;                 /* filter^2 / 12, finite and >= 0 */
+} mnr_atlas_args;
+int mnr_atlas_samples(const mnr_atlas_args* args, int64_t s0, int64_t n, float* means, float* covs, float* normals, float* viewdirs,
+                      int* face, void* stream);
+int mnr_atlas_store(const mnr_atlas_args* args, int64_t s0, int64_t n, const float* rgb, const int* face, unsigned char* atlas,
+                    unsigned char* mask, float* atlas_f32, void* stream);
+int mnr_atlas_uvs(const mnr_atlas_args* args, float* uv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,14 @@ class MeshClusterArgs(C.Structure):
               ('out_colors', vp), ('fallback', vp)]
 
 
+ATLAS_MIN_CELL = 3                 # MNR_ATLAS_MIN_CELL
+
+
+class AtlasArgs(C.Structure):
+  _fields_ = [('verts', vp), ('normals', vp), ('faces', vp), ('n_verts', C.c_int64), ('n_faces', C.c_int64), ('c', C.c_int), ('cols', C.c_int),
+              ('W', C.c_int), ('H', C.c_int), ('cov_scale', C.c_float)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('one_minus_b1', C.c_float),
@@ -330,6 +338,9 @@ _PROTOS = {
     'mnr_mesh_cluster_keys': ([vp, i64, C.POINTER(f32), f32, vp, vp], i32),
     'mnr_mesh_cluster_faces': ([vp, i64, vp, i64, i64, vp, vp, vp, vp, vp], i32),
     'mnr_mesh_cluster_solve': ([C.POINTER(MeshClusterArgs), vp], i32),
+    'mnr_atlas_samples': ([C.POINTER(AtlasArgs), i64, i64, vp, vp, vp, vp, vp, vp], i32),
+    'mnr_atlas_store': ([C.POINTER(AtlasArgs), i64, i64, vp, vp, vp, vp, vp, vp], i32),
+    'mnr_atlas_uvs': ([C.POINTER(AtlasArgs), vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

@@ -9,12 +9,15 @@
   mesh_stats     counts, Euler characteristic, open and non-manifold edges, signed volume, area (host, float64)
   filter_components / component_stats   connected components (ops.mesh_components, csrc/meshclean.hip): drop the small ones
   simplify       vertex clustering on a coarser grid with quadric-error placement (csrc/meshclean.hip)
+  bake_texture   a texture atlas of per-face charts, every texel queried with its own footprint's Gaussian (csrc/atlas.hip)
+  write_obj      OBJ + MTL + PNG of a mesh with a baked texture (write_ply takes the texture too)
 
 Grid convention (the kernels' own): field[i, j, k] sits at origin + spacing * (i, j, k), the linear point index is
 (i * ny + j) * nz + k, and a point is inside iff field >= level.
 """
 
 import math
+import os
 import time
 
 import numpy as np
@@ -402,6 +405,71 @@ def simplify(m, cell, origin=None, return_map=False):
   return out
 
 
+def _model_color_fn(model):
+  """The `color_fn` of `bake_texture` for a model: the NeRF MLP's rgb at the samples' Gaussians, with a zero GLO vector."""
+  plan = model.nerf_plan
+
+  def color_fn(means, covs, normals, viewdirs):
+    n = int(means.shape[0])
+    vd = viewdirs if plan.use_viewdirs else None
+    glo = torch.zeros((n, plan.glo), dtype=torch.float32, device=means.device) if plan.glo > 0 else None
+    return model.nerf_hp(None, (means[:, None], covs[:, None]), viewdirs=vd, glo_vec=glo)['rgb']
+
+  return color_fn
+
+
+def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT_CHUNK, cols=None, return_float=False):
+  """A texture atlas for the mesh dict `m` (vertices, normals, faces on the device): dict(texture [H,W,3] uint8, mask [H,W] uint8,
+  uv [T,3,2] float32, layout[, texture_f32 [H,W,3] float32 with return_float]) of device tensors.
+
+  The parameterisation is include/mnerf.h's contract (`ops.atlas_layout`): every face has a chart of its own, a right triangle of
+  `cell` texels a side, two to a cell of (cell + 1) x cell texels, the cells in a regular grid of `cols` columns (default: roughly
+  square).  It is closed-form, so two runs give the same atlas.  uv holds u, v of each face's three corners (v = 1 at the top
+  row); a bilinear lookup anywhere inside a face's UV triangle reads only texels that face owns, so there are no seams and no
+  padding.  mask is 255 on the texels a face owns and 0 elsewhere (an odd face count's spare half cell, a face with a vertex that is
+  not finite); texture is 0 there.
+
+  Every texel is coloured by color_fn(means [n,3], covs [n,3,3], normals [n,3], viewdirs [n,3]) -> rgb [n,3], called on `chunk`
+  samples at a time (`ops.atlas_samples`): the Gaussian has the texel's position on its face as mean and `filter`^2 / 12 times
+  the second moments of the texel's parallelogram as covariance (the integrated positional encoding then pre-filters the colour
+  to the texel's footprint; filter = 0 gives point samples), viewdirs is minus the interpolated normal.  texture =
+  floor(clip(rgb, 0, 1) * 255 + 0.5).  With model= the colour is `model.nerf_hp(None, (means[:, None], covs[:, None]), ...)['rgb']`
+  with a zero GLO vector, viewdirs / glo_vec passed only where the MLP reads them, as in `vertex_colors`; the preconditions of
+  `Model.mlp_call` apply: it is inference only, each chunk is evaluated at once (a few KiB a sample: lower `chunk` on a crowded
+  device), and it re-packs the bound parameters into the operand images a pending backward pass reads, so between a training
+  forward pass and its backward pass it may run only on the parameters that pass ran on.  Exactly one of color_fn and model is
+  given.  A mesh without faces gives a 0 x 0 texture and launches nothing.
+
+  What this is not: charts are uniform per face (a sliver gets as many texels as a fat triangle), there is no chart merging (mip
+  levels below 0 mix neighbouring cells), and the single head-on view direction bakes a specular lobe as seen along -normal."""
+  if (color_fn is None) == (model is None):
+    raise ValueError('bake_texture: exactly one of color_fn and model must be given')
+  if model is not None:
+    color_fn = _model_color_fn(model)
+  chunk = int(chunk)
+  if chunk < 1:
+    raise ValueError(f'bake_texture: chunk = {chunk} must be positive')
+  m = dict(vertices=m['vertices'].contiguous(), normals=m['normals'].contiguous(), faces=m['faces'].contiguous())
+  dev = m['vertices'].device
+  T = int(m['faces'].shape[0])
+  layout = ops.atlas_layout(T, cell, cols)
+  ops._chk_faces('bake_texture', m['faces'], m['vertices'].shape[0])           # once, not per chunk
+  H, W, total = layout['H'], layout['W'], layout['n_samples']
+  texture = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
+  mask = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+  texture_f32 = torch.zeros((H, W, 3), dtype=torch.float32, device=dev) if return_float else None
+  uv = ops.atlas_uvs(m, layout) if T > 0 else torch.zeros((0, 3, 2), dtype=torch.float32, device=dev)
+  for start in range(0, total, chunk):
+    stop = min(start + chunk, total)
+    means, covs, normals, viewdirs, face = ops.atlas_samples(m, layout, start, stop, filter=filter, check_faces=False)
+    rgb = color_fn(means, covs, normals, viewdirs).reshape(stop - start, 3).to(torch.float32).contiguous()
+    ops.atlas_store(m, layout, start, rgb, face, texture, mask, texture_f32, check_faces=False)
+  out = dict(texture=texture, mask=mask, uv=uv, layout=layout)
+  if return_float:
+    out['texture_f32'] = texture_f32
+  return out
+
+
 def _host(x, dtype):
   if x is None:
     return None
@@ -413,11 +481,33 @@ def _host(x, dtype):
 _VERTEX_FIELDS = [(n, '<f4') for n in ('x', 'y', 'z', 'nx', 'ny', 'nz')]
 _COLOR_FIELDS = [(n, 'u1') for n in ('red', 'green', 'blue')]
 _FACE_DTYPE = np.dtype([('n', 'u1'), ('v', '<i4', (3,))])
+_FACE_UV_DTYPE = np.dtype([('n', 'u1'), ('v', '<i4', (3,)), ('nt', 'u1'), ('t', '<f4', (6,))])
+_FACE_PROPS = [['list', 'uchar', 'int', 'vertex_indices']]
+_FACE_UV_PROPS = _FACE_PROPS + [['list', 'uchar', 'float', 'texcoord']]
 
 
-def write_ply(path, mesh):
+def _texture_arrays(name, texture, n_faces):
+  """(image [H,W,3] uint8, uv [T,3,2] float32) on the host of a `bake_texture` result."""
+  image, uv = _host(texture['texture'], np.uint8), _host(texture['uv'], np.float32)
+  if image.ndim != 3 or image.shape[2] != 3 or image.shape[0] == 0 or image.shape[1] == 0:
+    raise ValueError(f'{name}: the texture must be a non-empty [H,W,3] image, is {image.shape}')
+  if uv.shape != (n_faces, 3, 2):
+    raise ValueError(f'{name}: uv must be [{n_faces},3,2] (three corners a face), is {uv.shape}')
+  return image, uv
+
+
+def _write_png(path, image):
+  from PIL import Image
+  Image.fromarray(image, 'RGB').save(path, format='PNG')
+
+
+def write_ply(path, mesh, texture=None):
   """dict(vertices, normals, faces[, colors]) (device or host arrays) as a PLY file, binary_little_endian 1.0: vertex
-  properties x y z nx ny nz (float) and red green blue (uchar) when the mesh has colours; faces as `list uchar int vertex_indices`."""
+  properties x y z nx ny nz (float) and red green blue (uchar) when the mesh has colours; faces as `list uchar int vertex_indices`.
+
+  With `texture` (the dict `bake_texture` returns) a face also carries `list uchar float texcoord`, u v of its three corners (the
+  layout MeshLab writes and reads), the header names the image in `comment TextureFile <name>.png`, and the image is written as
+  <path without extension>.png next to the file.  Without it the file is byte for byte the one written before textures existed."""
   verts, normals = _host(mesh['vertices'], np.float32).reshape(-1, 3), _host(mesh['normals'], np.float32).reshape(-1, 3)
   faces, colors = _host(mesh['faces'], np.int32).reshape(-1, 3), _host(mesh.get('colors'), np.uint8)
   if normals.shape != verts.shape or (colors is not None and colors.reshape(-1, 3).shape != verts.shape):
@@ -430,28 +520,41 @@ def write_ply(path, mesh):
   if colors is not None:
     for c, n in enumerate(('red', 'green', 'blue')):
       v[n] = colors.reshape(-1, 3)[:, c]
-  f = np.zeros((faces.shape[0],), dtype=_FACE_DTYPE)
+  f = np.zeros((faces.shape[0],), dtype=_FACE_DTYPE if texture is None else _FACE_UV_DTYPE)
   f['n'] = 3
   f['v'] = faces
-  header = ['ply', 'format binary_little_endian 1.0', f'element vertex {verts.shape[0]}']
+  header = ['ply', 'format binary_little_endian 1.0']
+  if texture is not None:
+    image, uv = _texture_arrays('write_ply', texture, faces.shape[0])
+    png = os.path.splitext(path)[0] + '.png'
+    f['nt'] = 6
+    f['t'] = uv.reshape(-1, 6)
+    header += [f'comment TextureFile {os.path.basename(png)}']
+  header += [f'element vertex {verts.shape[0]}']
   header += [f'property {"uchar" if t == "u1" else "float"} {n}' for n, t in fields]
-  header += [f'element face {faces.shape[0]}', 'property list uchar int vertex_indices', 'end_header']
+  header += [f'element face {faces.shape[0]}', 'property list uchar int vertex_indices']
+  if texture is not None:
+    header += ['property list uchar float texcoord']
+  header += ['end_header']
   with open(path, 'wb') as fh:
     fh.write(('\n'.join(header) + '\n').encode('ascii'))
     fh.write(v.tobytes())
     fh.write(f.tobytes())
+  if texture is not None:
+    _write_png(png, image)
 
 
 def read_ply(path):
   """A file written by `write_ply` as dict(vertices [V,3] float32, normals [V,3] float32, faces [T,3] int32,
-  colors [V,3] uint8 or None) of host arrays."""
+  colors [V,3] uint8 or None) of host arrays; a file with texture coordinates adds texcoord [T,3,2] float32 and texture_file,
+  the name in its `comment TextureFile` line (None without one)."""
   with open(path, 'rb') as fh:
     data = fh.read()
   end = data.index(b'end_header\n') + len(b'end_header\n')
   lines = data[:end].decode('ascii').split('\n')
   if lines[0] != 'ply' or lines[1] != 'format binary_little_endian 1.0':
     raise ValueError(f'{path}: not a binary_little_endian 1.0 PLY file')
-  counts, props, element = {}, {}, None
+  counts, props, element, texture_file = {}, {}, None, None
   for line in lines[2:]:
     w = line.split()
     if w[:1] == ['element']:
@@ -459,17 +562,49 @@ def read_ply(path):
       counts[element], props[element] = int(w[2]), []
     elif w[:1] == ['property']:
       props[element].append(w[1:])
+    elif w[:2] == ['comment', 'TextureFile']:
+      texture_file = line.split(None, 2)[2]
   fields = [(p[-1], {'float': '<f4', 'uchar': 'u1'}[p[0]]) for p in props.get('vertex', [])]
-  if fields[:6] != _VERTEX_FIELDS or fields[6:] not in ([], _COLOR_FIELDS) or props.get('face') != [['list', 'uchar', 'int', 'vertex_indices']]:
+  if fields[:6] != _VERTEX_FIELDS or fields[6:] not in ([], _COLOR_FIELDS) or props.get('face') not in (_FACE_PROPS, _FACE_UV_PROPS):
     raise ValueError(f'{path}: not the layout write_ply writes')
+  textured = props['face'] == _FACE_UV_PROPS
   V, T = counts['vertex'], counts['face']
   v = np.frombuffer(data, dtype=np.dtype(fields), count=V, offset=end)
-  f = np.frombuffer(data, dtype=_FACE_DTYPE, count=T, offset=end + V * v.dtype.itemsize)
-  if T and not (f['n'] == 3).all():
+  f = np.frombuffer(data, dtype=_FACE_UV_DTYPE if textured else _FACE_DTYPE, count=T, offset=end + V * v.dtype.itemsize)
+  if T and not ((f['n'] == 3).all() and (not textured or (f['nt'] == 6).all())):
     raise ValueError(f'{path}: a face that is no triangle')
   col = lambda names: np.stack([v[n] for n in names], -1) if V else np.zeros((0, 3), dtype=v.dtype[names[0]])
-  return dict(vertices=col(('x', 'y', 'z')), normals=col(('nx', 'ny', 'nz')), faces=np.array(f['v'], dtype=np.int32).reshape(T, 3),
-              colors=col(('red', 'green', 'blue')) if len(fields) > 6 else None)
+  out = dict(vertices=col(('x', 'y', 'z')), normals=col(('nx', 'ny', 'nz')), faces=np.array(f['v'], dtype=np.int32).reshape(T, 3),
+             colors=col(('red', 'green', 'blue')) if len(fields) > 6 else None)
+  if textured:
+    out['texcoord'], out['texture_file'] = np.array(f['t'], dtype=np.float32).reshape(T, 3, 2), texture_file
+  return out
+
+
+def write_obj(path, mesh, texture):
+  """dict(vertices, normals, faces) with the dict `bake_texture` returns as a Wavefront OBJ: <path> with `v`, `vn` (one a vertex),
+  3 T `vt` lines (u v of each face's corners: a vertex has one UV per face it is in) and `f v/vt/vn` lines, 1-based;
+  <path without extension>.mtl with one material whose map_Kd is <path without extension>.png, the texture.  Vertex colours are
+  not written: OBJ has no standard place for them."""
+  verts, normals = _host(mesh['vertices'], np.float32).reshape(-1, 3), _host(mesh['normals'], np.float32).reshape(-1, 3)
+  faces = _host(mesh['faces'], np.int32).reshape(-1, 3)
+  if normals.shape != verts.shape:
+    raise ValueError('write_obj: normals must have one row per vertex')
+  image, uv = _texture_arrays('write_obj', texture, faces.shape[0])
+  base = os.path.splitext(path)[0]
+  name = os.path.basename(base)
+  num = lambda row: ' '.join(f'{float(x):.9g}' for x in row)
+  lines = [f'mtllib {name}.mtl', f'o {name}']
+  lines += ['v ' + num(r) for r in verts]
+  lines += ['vn ' + num(r) for r in normals]
+  lines += ['vt ' + num(r) for r in uv.reshape(-1, 2)]
+  lines += ['usemtl material0']
+  lines += ['f ' + ' '.join(f'{int(i) + 1}/{3 * t + k + 1}/{int(i) + 1}' for k, i in enumerate(row)) for t, row in enumerate(faces)]
+  with open(path, 'w') as fh:
+    fh.write('\n'.join(lines) + '\n')
+  with open(base + '.mtl', 'w') as fh:
+    fh.write('\n'.join(['newmtl material0', 'Ka 1 1 1', 'Kd 1 1 1', 'Ks 0 0 0', 'illum 1', f'map_Kd {name}.png']) + '\n')
+  _write_png(base + '.png', image)
 
 
 def mesh_stats(verts, faces):

@@ -1798,3 +1798,114 @@ def mesh_cluster_solve(verts, normals, colors, faces, keys, member_start, member
   a.out_verts, a.out_normals, a.out_colors, a.fallback = out_v.data_ptr(), out_n.data_ptr(), _ptr(out_c), fallback.data_ptr()
   L.check(lib().mnr_mesh_cluster_solve(C.byref(a), _stream()))
   return out_v, out_n, out_c, fallback
+
+
+# ----------------------------------------------------------------------------- texture atlas (csrc/atlas.hip)
+
+def atlas_layout(n_faces, cell, cols=None):
+  """dict(cell, cols, rows, W, H, n_samples) of the atlas of `n_faces` faces at a cell of `cell` texels (include/mnerf.h): faces
+  2k and 2k + 1 share cell k, a cell is (cell + 1) x cell texels, cells fill the atlas row-major `cols` to a row, W = cols (cell + 1),
+  rows = ceil(ncells / cols), H = rows cell, n_samples = ncells cell (cell + 1).  The default cols is max(1, ceil(sqrt(ncells cell /
+  (cell + 1)))), in integers, which makes the atlas roughly square.  No faces: rows = W = H = n_samples = 0.  Pure Python: the
+  one place the layout arithmetic lives on the host."""
+  n_faces, cell = int(n_faces), int(cell)
+  if cell < L.ATLAS_MIN_CELL:
+    raise ValueError(f'atlas_layout: cell = {cell} must be at least {L.ATLAS_MIN_CELL} texels')
+  if not 0 <= n_faces < 2 ** 31:
+    raise ValueError(f'atlas_layout: {n_faces} faces: must lie in 0 .. 2^31 - 1')
+  ncells = (n_faces + 1) // 2
+  if cols is None:
+    cols = math.isqrt(ncells * cell // (cell + 1))
+    while cols * cols * (cell + 1) < ncells * cell:
+      cols += 1
+    cols = max(1, cols)
+  cols = int(cols)
+  if cols < 1:
+    raise ValueError(f'atlas_layout: cols = {cols} must be at least 1')
+  rows = -(-ncells // cols)
+  W, H = (cols * (cell + 1) if ncells else 0), rows * cell
+  if W >= 2 ** 31 or H >= 2 ** 31:
+    raise ValueError(f'atlas_layout: an atlas of {W} x {H} texels: both sides must stay below 2^31')
+  return dict(cell=cell, cols=cols, rows=rows, W=W, H=H, n_samples=ncells * cell * (cell + 1))
+
+
+def _atlas_args(name, m, layout, filter=1.0, check_faces=True):
+  """(AtlasArgs, the tensors it points to) of a mesh dict and an `atlas_layout`; face indices outside the vertices raise ValueError
+  (one min / max read-back; check_faces=False is for a caller that has made that check on this mesh, as mesh.bake_texture does
+  once for all its chunks: the kernels never read outside the vertices, such a face's samples are invalid)."""
+  verts, normals, faces = m['vertices'], m['normals'], m['faces']
+  _chk(verts, f32, f'{name}: vertices')
+  _chk(normals, f32, f'{name}: normals')
+  if verts.dim() != 2 or verts.shape[1] != 3 or normals.shape != verts.shape:
+    raise ValueError(f'{name}: vertices and normals must be [V,3], are {tuple(verts.shape)} and {tuple(normals.shape)}')
+  if check_faces:
+    V, T = _chk_faces(name, faces, verts.shape[0])
+  else:
+    _chk(faces, torch.int32, f'{name}: faces')
+    V, T = int(verts.shape[0]), int(faces.shape[0])
+    if tuple(faces.shape) != (T, 3):
+      raise ValueError(f'{name}: faces must be [T,3], is {tuple(faces.shape)}')
+  if layout != atlas_layout(T, layout['cell'], layout['cols']):
+    raise ValueError(f'{name}: the layout {layout} is not atlas_layout({T}, {layout["cell"]}, {layout["cols"]})')
+  filter = float(filter)
+  if not (filter >= 0. and math.isfinite(filter)):
+    raise ValueError(f'{name}: filter = {filter} must be finite and not negative')
+  a = L.AtlasArgs()
+  a.verts, a.normals, a.faces, a.n_verts, a.n_faces = verts.data_ptr(), normals.data_ptr(), faces.data_ptr(), V, T
+  a.c, a.cols, a.W, a.H = layout['cell'], layout['cols'], layout['W'], layout['H']
+  a.cov_scale = filter * filter / 12.
+  return a, (verts, normals, faces)
+
+
+def _atlas_chunk(name, layout, start, stop):
+  start, stop = int(start), int(stop)
+  if not 0 <= start <= stop <= layout['n_samples'] or stop - start >= 2 ** 31:
+    raise ValueError(f'{name}: samples {start} .. {stop} of {layout["n_samples"]}: a chunk lies inside the atlas and has fewer than 2^31 samples')
+  return start, stop - start
+
+
+def atlas_samples(m, layout, start, stop, filter=1.0, check_faces=True):
+  """(means [n,3], covs [n,3,3], normals [n,3], viewdirs [n,3] float32, face [n] int32) of the atlas samples start .. stop - 1 of the
+  mesh dict `m` (vertices, normals, faces on the device) under `layout` = atlas_layout(T, cell, cols) (mnr_atlas_samples;
+  include/mnerf.h): sample s = cell c (c + 1) + Y (c + 1) + X is a texel, its Gaussian has the texel's position on its face as
+  mean and filter^2 / 12 times the second moments of the texel's parallelogram as covariance (filter = 0: a point), its view
+  direction is minus the interpolated normal.  face = -1 marks the invalid samples (an odd face count's spare half cell, a face with
+  a vertex that is not finite): zero mean and covariance, direction (0, 0, 1)."""
+  a, keep = _atlas_args('atlas_samples', m, layout, filter, check_faces)
+  s0, n = _atlas_chunk('atlas_samples', layout, start, stop)
+  dev = keep[0].device
+  means, normals, viewdirs = (torch.empty((n, 3), dtype=f32, device=dev) for _ in range(3))
+  covs = torch.empty((n, 3, 3), dtype=f32, device=dev)
+  face = torch.empty((n,), dtype=torch.int32, device=dev)
+  L.check(lib().mnr_atlas_samples(C.byref(a), s0, n, _ptr(means), _ptr(covs), _ptr(normals), _ptr(viewdirs), _ptr(face), _stream()))
+  return means, covs, normals, viewdirs, face
+
+
+def atlas_store(m, layout, start, rgb, face, atlas, mask, atlas_f32=None, check_faces=True):
+  """Write the colours rgb [n,3] float32 of the samples start .. start + n - 1 into atlas [H,W,3] uint8 as floor(clip(rgb, 0, 1) *
+  255 + 0.5), set mask [H,W] uint8 to 255 there and, when given, atlas_f32 [H,W,3] float32 to rgb itself (mnr_atlas_store).  face [n]
+  int32 is `atlas_samples`' output: samples with face < 0 are skipped.  In place; every texel belongs to one sample."""
+  name = 'atlas_store'
+  a, keep = _atlas_args(name, m, layout, check_faces=check_faces)
+  _chk(rgb, f32, f'{name}: rgb')
+  _chk(face, torch.int32, f'{name}: face')
+  _chk(atlas, torch.uint8, f'{name}: atlas')
+  _chk(mask, torch.uint8, f'{name}: mask')
+  _chk(atlas_f32, f32, f'{name}: atlas_f32', allow_none=True)
+  n = int(face.shape[0])
+  H, W = layout['H'], layout['W']
+  if tuple(rgb.shape) != (n, 3) or face.dim() != 1:
+    raise ValueError(f'{name}: rgb must be [n,3] and face [n], are {tuple(rgb.shape)} and {tuple(face.shape)}')
+  if tuple(atlas.shape) != (H, W, 3) or tuple(mask.shape) != (H, W) or (atlas_f32 is not None and tuple(atlas_f32.shape) != (H, W, 3)):
+    raise ValueError(f'{name}: atlas (and atlas_f32) must be [{H},{W},3] and mask [{H},{W}]')
+  s0, n = _atlas_chunk(name, layout, start, int(start) + n)
+  L.check(lib().mnr_atlas_store(C.byref(a), s0, n, _ptr(rgb), _ptr(face), _ptr(atlas), _ptr(mask), _ptr(atlas_f32), _stream()))
+
+
+def atlas_uvs(m, layout):
+  """uv [T,3,2] float32: (u, v) of the three corners of every face in the atlas of `layout` (mnr_atlas_uvs; include/mnerf.h), the
+  inverse of `atlas_samples`' texel -> surface map: u = px / W, v = 1 - py / H with row 0 the top of the image."""
+  a, keep = _atlas_args('atlas_uvs', m, layout)
+  uv = torch.empty((int(a.n_faces), 3, 2), dtype=f32, device=keep[0].device)
+  L.check(lib().mnr_atlas_uvs(C.byref(a), _ptr(uv), _stream()))
+  return uv

@@ -1,0 +1,26 @@
+"""tests/test_gpu_atlas.py run on the kernel-source simulator in a child pytest (MNR_TESTS_ON_SIMULATOR=1, the way
+tests/test_sim_mesh_clean.py runs its file): the three kernels of csrc/atlas.hip through the product's own host code against the
+NumPy restatement, seam safety, linearity, the analytic bake and the degenerate inputs, with the test code unchanged.  The model
+and the script are left to the MI355X: the model bake takes minutes on the simulator and runs no kernel of this file's subject
+that the other tests do not."""
+
+import os
+import shutil
+import subprocess
+import sys
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+pytestmark = pytest.mark.skipif(not (shutil.which('clang++') or os.path.exists('/opt/rocm/lib/llvm/bin/clang++')),
+                                reason='needs clang++')
+
+
+def test_atlas_kernels_pass_on_the_simulator():
+  env = dict(os.environ, MNR_TESTS_ON_SIMULATOR='1')
+  cmd = [sys.executable, '-m', 'pytest', '-q', '-m', 'gpu', '-p', 'no:cacheprovider', 'tests/test_gpu_atlas.py', '-k', 'not script and not model']
+  r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
+  tail = '\n'.join((r.stdout + r.stderr).splitlines()[-25:])
+  assert r.returncode == 0, tail
+  assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail, tail
