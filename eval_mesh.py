@@ -1,0 +1,112 @@
+#!/usr/bin/env python
+"""Mesh evaluation script: render a mesh file from the cameras of a dataset split and score it against the split's images.
+
+The mesh is a PLY that `mesh.write_ply` wrote (extract_mesh.py's output): with per-face texture coordinates it is rendered with the
+PNG its `comment TextureFile` line names (looked up next to the file), otherwise with its vertex colours, otherwise as shaded
+normals.  Every view is rasterised on the device (`mesh.render_mesh`, csrc/raster.hip) and scored by `image.MetricHarness` (PSNR and
+SSIM), honouring Config.eval_quantize_metrics and Config.eval_crop_borders as eval.py does.  No checkpoint is needed.  Perspective
+cameras only: a dataset whose cameras `mesh.world_to_pixel` refuses (lens distortion, NDC rays, fisheye) fails with its message.
+
+Under --out_dir (default: <mesh file's directory>/mesh_eval) it writes mesh_color_NNN.png for every view and, in eval.py's format
+(one line, values separated by blanks), mesh_metric_psnr.txt, mesh_metric_ssim.txt and mesh_render_times.txt (seconds a view:
+visibility and shading, bracketed by a device synchronisation).
+
+  python eval_mesh.py --mesh garden.ply --gin_configs configs/360.gin --gin_bindings "Config.data_dir = '...'" --supersample 2
+"""
+
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+from multinerf_amd import configs, datasets, image, mesh
+
+
+def parse_args(argv):
+  ap = argparse.ArgumentParser()
+  ap.add_argument('--mesh', required=True, help='a PLY file written by mesh.write_ply / extract_mesh.py')
+  ap.add_argument('--gin_configs', action='append', default=[])
+  ap.add_argument('--gin_bindings', action='append', default=[])
+  ap.add_argument('--preset', default=None)
+  ap.add_argument('--split', choices=('train', 'test'), default='test', help='the cameras and images to score against')
+  ap.add_argument('--out_dir', default=None, help='default: <directory of --mesh>/mesh_eval')
+  ap.add_argument('--supersample', type=int, default=1, help='render k x k samples a pixel and box-average them')
+  ap.add_argument('--near', type=float, default=None, help='surface nearer than this (zc) is not seen; default: Config.near')
+  ap.add_argument('--bg', default='1,1,1', help='r,g,b of the pixels no face covers')
+  ap.add_argument('--cull', choices=('none', 'back'), default='none')
+  args = ap.parse_args(argv)
+  try:
+    args.bg = [float(v) for v in args.bg.split(',')]
+    if len(args.bg) != 3:
+      raise ValueError
+  except ValueError:
+    raise SystemExit(f'eval_mesh.py: --bg must be three numbers r,g,b') from None
+  if args.supersample < 1:
+    raise SystemExit('eval_mesh.py: --supersample must be at least 1')
+  return args
+
+
+def load_mesh(path, device):
+  """(mesh dict on the device, texture dict or None, colours or None) of a PLY file."""
+  m = mesh.read_ply(path)
+  dm = {k: torch.from_numpy(np.ascontiguousarray(m[k])).to(device) for k in ('vertices', 'normals', 'faces')}
+  texture = colors = None
+  if m.get('texcoord') is not None:
+    if not m.get('texture_file'):
+      raise SystemExit(f'eval_mesh.py: {path} has texture coordinates but no `comment TextureFile` line')
+    from PIL import Image
+    png = os.path.join(os.path.dirname(os.path.abspath(path)), m['texture_file'])
+    pixels = np.ascontiguousarray(np.asarray(Image.open(png).convert('RGB'), dtype=np.uint8))
+    texture = dict(texture=torch.from_numpy(pixels).to(device), uv=torch.from_numpy(np.ascontiguousarray(m['texcoord'])).to(device))
+  elif m.get('colors') is not None:
+    colors = torch.from_numpy(np.ascontiguousarray(m['colors'])).to(device)
+  return dm, texture, colors
+
+
+def main(argv=None):
+  args = parse_args(sys.argv[1:] if argv is None else argv)
+  dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
+  torch.cuda.set_device(dev)
+  config = configs.load_preset(args.preset, args.gin_bindings) if args.preset else \
+      configs.load_config(args.gin_configs, args.gin_bindings, save_config=False)
+  near = float(config.near if args.near is None else args.near)
+  dm, texture, colors = load_mesh(args.mesh, dev)
+  source = 'texture' if texture is not None else 'vertex colours' if colors is not None else 'shaded normals'
+  print(f'{args.mesh}: {dm["vertices"].shape[0]} vertices, {dm["faces"].shape[0]} faces, colour from {source}')
+  dataset = datasets.load_dataset(args.split, config.data_dir, config, device=dev)
+  camtype = 'pano' if getattr(dataset, '_render_spherical', False) else dataset.camtype
+  pixtocams = mesh._host(dataset.pixtocams, np.float64)
+  out_dir = args.out_dir or os.path.join(os.path.dirname(os.path.abspath(args.mesh)), 'mesh_eval')
+  os.makedirs(out_dir, exist_ok=True)
+  harness = image.MetricHarness()
+  quant, crop = bool(config.eval_quantize_metrics), int(config.eval_crop_borders)
+  to_u8 = image.quantize_u8 if quant else (lambda x: (x.clamp(0, 1).cpu().numpy() * 255 + 0.5).astype(np.uint8))
+  n = min(dataset.size, config.eval_dataset_limit)
+  psnrs, ssims, seconds = [], [], []
+  from PIL import Image
+  for idx in range(n):
+    proj = mesh.world_to_pixel(pixtocams if pixtocams.ndim == 2 else pixtocams[idx], dataset.camtoworlds[idx],
+                               distortion_params=dataset.distortion_params, pixtocam_ndc=dataset.pixtocam_ndc, camtype=camtype)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    r = mesh.render_mesh(dm, None, None, dataset.height, dataset.width, texture=texture, colors=colors, near=near, bg=args.bg, cull=args.cull,
+                         supersample=args.supersample, proj=proj)
+    torch.cuda.synchronize()
+    seconds.append(time.time() - t0)
+    gt = torch.as_tensor(dataset.images[idx]).to(device=dev, dtype=torch.float32)[..., :3].contiguous()
+    metric = harness(r['rgb'].contiguous(), gt, quantize=quant, crop=crop)
+    psnrs.append(metric['psnr'])
+    ssims.append(metric['ssim'])
+    print(f'Mesh image {idx + 1}/{n}: {seconds[-1]:.4f}s, psnr {metric["psnr"]:.3f}, ssim {metric["ssim"]:.4f}', flush=True)
+    Image.fromarray(to_u8(r['rgb'])).save(os.path.join(out_dir, f'mesh_color_{idx:03d}.png'))
+  print(f'Average mesh psnr over {n} images: {np.mean(psnrs):.3f}, ssim {np.mean(ssims):.4f}')
+  for name, values in (('mesh_metric_psnr.txt', psnrs), ('mesh_metric_ssim.txt', ssims), ('mesh_render_times.txt', seconds)):
+    with open(os.path.join(out_dir, name), 'w') as f:
+      f.write(' '.join(str(v) for v in values))
+
+
+if __name__ == '__main__':
+  main()

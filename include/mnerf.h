@@ -1137,6 +1137,92 @@ int mnr_atlas_store(const mnr_atlas_args* args, int64_t s0, int64_t n, const flo
                     unsigned char* mask, float* atlas_f32, void* stream);
 int mnr_atlas_uvs(const mnr_atlas_args* args, float* uv, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Mesh rasteriser: a visibility buffer and its shading  (csrc/raster.hip)
+ * 2D homogeneous rasterisation (Olano and Greer 1997): the edge functions come from the homogeneous vertices, nothing is clipped,
+ * and a triangle that crosses the camera plane is no special case.  proj [3,4] is the matrix of the TSDF section (mesh.world_to_pixel):
+ * P (X, 1) = (u zc, v zc, zc), pixel (x, y) has its centre at (x + .5, y + .5) and zc is the rendered distance.  Everything is float32
+ * in the order written, no contraction; a NumPy restatement (tests/raster_ref.py) follows it exactly, every face against every pixel.
+ *
+ * Per vertex  h_v[r] = ((P[r][0] x + P[r][1] y) + P[r][2] z) + P[r][3], r = 0, 1, 2: it depends on the vertex only, so every face
+ *             that uses a vertex sees the same three numbers.
+ * Per face    (corners 0, 1, 2; (i, j, k) cyclic)  n_i = h_j x h_k, i.e. n_i.x = h_j.y h_k.z - h_j.z h_k.y, n_i.y = h_j.z h_k.x -
+ *             h_j.x h_k.z, n_i.z = h_j.x h_k.y - h_j.y h_k.x;  det = (n_0.x h_0.x + n_0.y h_0.y) + n_0.z h_0.z;  s = sign(det).
+ *             A face is SKIPPED if it has an index outside [0, n_verts), a coordinate of h that is not finite, or a det that is 0
+ *             or not finite; with cull = MNR_RASTER_CULL_BACK also if det > 0 (see `front` below).
+ * Per pixel   E_i = ((s n_i.x)(x + .5) + (s n_i.y)(y + .5)) + s n_i.z;  S = (E_0 + E_1) + E_2;  zc = |det| / S.
+ * Covered     iff for every i: E_i > 0, or E_i == 0 and tie(s n_i);  and S > 0;  and zc is finite;  and zc > near;  and the pixel
+ *             lies in the face's pixel box (below).  tie(a, b, c) = a > 0 or (a == 0 and (b > 0 or (b == 0 and c > 0))).
+ * Resolve     vis[y, x] = the minimum of key = (bits(zc) << 32) | face over the covering faces (zc > 0: its bit pattern is
+ *             monotone; the nearest face wins, among equal depths the lowest id); all ones where no face covers the pixel.
+ *
+ * Why this form.  The face across an edge computes h_k x h_j, which without contraction is exactly -n_i, so for two faces of one
+ * orientation a pixel centre is on opposite sides of the shared edge, or exactly on it for both, and then tie() gives it to exactly
+ * one: no cracks and no double hits across an edge, by construction.  E_i / S are the perspective-correct barycentrics, |det| / S
+ * is the zc of the surface point, and S > 0 with every E_i >= 0 implies that the point lies in front of the camera plane.
+ * LIMIT.  The argument is per EDGE.  Where a vertex of a fan projects within rounding of a pixel centre, the fan's rounded edge
+ * lines need not meet in one point and that one pixel can be claimed by no face of the fan, or by several.  Curing it needs vertices
+ * snapped to fixed point, which cannot represent a vertex behind the camera; it is not done.
+ * `front`.  For a P whose left 3 x 3 block has a positive determinant (world_to_pixel's always has: K diag(1, -1, -1) R^T with
+ * det K > 0) a face whose corners run counter-clockwise seen from the camera, i.e. whose geometric normal (v1 - v0) x (v2 - v0)
+ * faces the camera, has det < 0: the flip of y makes pixel space left-handed as seen on the screen.  MNR_RASTER_CULL_BACK keeps
+ * exactly those.
+ *
+ * Pixel box.  If all three h.z > 0: with a = h.x / h.z (h.y / h.z) of the three corners (float32 divisions), the columns (rows)
+ * max(floor(min a) - 1, 0) .. min(floor(max a) + 1, W - 1 (H - 1)), none if that is empty.  If all three h.z <= 0 (the face lies
+ * wholly behind the camera plane): none.  Otherwise (it crosses the plane): the whole image.  In exact arithmetic a covered centre
+ * lies inside the box of the projected corners, the pixel of margin keeps the rounding of a and of well-conditioned edge
+ * functions from excluding one, and a face behind the plane covers nothing: sum_i E_i h_i.z = |det| > 0 needs an h_i.z > 0.  The box is nevertheless a CLAUSE of the coverage test and not only a
+ * prune: the edge functions of a sliver are differences of products that cancel almost completely, their signs far from the
+ * sliver are rounding noise, and without the clause such a face claims stray pixels with a meaningless zc (a face of 0.001 pixel
+ * of a 10364-face sphere claimed a pixel 1.8 pixels away, in front of everything).  Inside its box a sliver's coverage and zc
+ * remain noise; and where the noise of an edge exceeds the pixel of margin (|u|, |v| far beyond 10^4) the clause can open a crack.
+ * A face whose box holds more than `threshold` pixels takes the large-face path (a workgroup per face), the others
+ * the small-face path (a thread per face); both run the same coverage function, so threshold = 0 (all large), any value in
+ * between and a huge one (all small) write the same buffer bit for bit.  list [n_faces] and count [1] are the workspace of the
+ * large-face list; what they hold afterwards is not specified (the list's order depends on arrival, the buffer does not).
+ * The only atomics are integer: a 64-bit unsigned atomicMin per covered pixel and an atomicAdd per wave for the list.
+ *
+ * mnr_raster_visibility fills vis [H,W] and resolves.  mnr_raster_shade, a thread a pixel, decodes the winner f, recomputes E_i, S
+ * and zc (the same code, the same bits) and writes, with l_i = E_i / S:
+ *   face [H,W] = f, depth [H,W] = zc, acc [H,W] = 1, bary [H,W,3] = l;
+ *   normals [H,W,3]: n = (l_0 n_0 + l_1 n_1) + l_2 n_2 of the vertex normals over len = sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2) where
+ *     0 < len < inf; else the face normal (v1 - v0) x (v2 - v0) (the atlas section's formula) over its length under the same
+ *     condition; else (0, 0, 1);
+ *   rgb [H,W,3]: with colors [n_verts,3] (uint8: c / 255.f first) c = (l_0 c_0 + l_1 c_1) + l_2 c_2.
+ *     With texture [Ht,Wt,3] (uint8: t / 255.f first) and uv [n_faces,3,2] (u, v of each face's corners, v = 1 the top row, what
+ *     mnr_atlas_uvs writes): (u, v) blended like c;  x = u float(Wt) - .5, y = (1 - v) float(Ht) - .5;  xf = floor(x), fx = x - xf,
+ *     columns xa = clamp(int(xf), 0, Wt - 1) and xb = clamp(int(xf) + 1, 0, Wt - 1), rows ya, yb likewise;
+ *     top = (1 - fx) t[ya,xa] + fx t[ya,xb],  bot = (1 - fx) t[yb,xa] + fx t[yb,xb],  rgb = (1 - fy) top + fy bot.
+ *     With neither: the shaded normal 0.5 + 0.5 n.  colors and texture together are refused.
+ * A pixel without a winner (all ones, or a key that names no rasterisable face) gets face -1, depth 0, acc 0, bary 0, normals 0 and
+ * rgb = bg.  depth and acc are what mnr_tsdf_integrate takes.  n_faces == 0: the buffer is filled and nothing else is launched.
+ * H, W >= 1; near > 0 and finite; n_faces < 2^31 - 1.
+ * ------------------------------------------------------------------------- */
+#define MNR_RASTER_CULL_NONE 0
+#define MNR_RASTER_CULL_BACK 1
+typedef struct {
+  const float* verts;              /* [n_verts,3] */
+  const float* normals;            /* [n_verts,3] (shade) */
+  const int* faces;                /* [n_faces,3] */
+  int64_t n_verts, n_faces;
+  float proj[12];                  /* [3,4], row-major */
+  int H, W;
+  float near;                      /* > 0, finite */
+  int cull;                        /* MNR_RASTER_CULL_* (visibility) */
+  int64_t threshold;               /* >= 0: box pixels above which a face takes the large-face path (visibility) */
+  const void* colors;              /* [n_verts,3] float or uint8, or NULL (shade) */
+  int colors_u8;
+  const void* texture;             /* [Ht,Wt,3] float or uint8, or NULL (shade) */
+  int texture_u8;
+  int Ht, Wt;
+  const float* uv;                 /* [n_faces,3,2], with a texture (shade) */
+  float bg[3];
+} mnr_raster_args;
+int mnr_raster_visibility(const mnr_raster_args* args, uint64_t* vis, int* list, int* count, void* stream);
+int mnr_raster_shade(const mnr_raster_args* args, const uint64_t* vis, int* face, float* depth, float* acc, float* bary, float* normals,
+                     float* rgb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

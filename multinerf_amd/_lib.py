@@ -238,6 +238,16 @@ class AtlasArgs(C.Structure):
               ('W', C.c_int), ('H', C.c_int), ('cov_scale', C.c_float)]
 
 
+RASTER_CULL = {'none': 0, 'back': 1}           # MNR_RASTER_CULL_*
+
+
+class RasterArgs(C.Structure):
+  _fields_ = [('verts', vp), ('normals', vp), ('faces', vp), ('n_verts', C.c_int64), ('n_faces', C.c_int64), ('proj', C.c_float * 12),
+              ('H', C.c_int), ('W', C.c_int), ('near', C.c_float), ('cull', C.c_int), ('threshold', C.c_int64), ('colors', vp),
+              ('colors_u8', C.c_int), ('texture', vp), ('texture_u8', C.c_int), ('Ht', C.c_int), ('Wt', C.c_int), ('uv', vp),
+              ('bg', C.c_float * 3)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('one_minus_b1', C.c_float),
@@ -341,6 +351,8 @@ _PROTOS = {
     'mnr_atlas_samples': ([C.POINTER(AtlasArgs), i64, i64, vp, vp, vp, vp, vp, vp], i32),
     'mnr_atlas_store': ([C.POINTER(AtlasArgs), i64, i64, vp, vp, vp, vp, vp, vp], i32),
     'mnr_atlas_uvs': ([C.POINTER(AtlasArgs), vp, vp], i32),
+    'mnr_raster_visibility': ([C.POINTER(RasterArgs), vp, vp, vp, vp], i32),
+    'mnr_raster_shade': ([C.POINTER(RasterArgs), vp, vp, vp, vp, vp, vp, vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

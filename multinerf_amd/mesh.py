@@ -11,6 +11,7 @@
   simplify       vertex clustering on a coarser grid with quadric-error placement (csrc/meshclean.hip)
   bake_texture   a texture atlas of per-face charts, every texel queried with its own footprint's Gaussian (csrc/atlas.hip)
   write_obj      OBJ + MTL + PNG of a mesh with a baked texture (write_ply takes the texture too)
+  render_mesh    rasterise a mesh from a camera: face ids, depth, barycentrics, normals, colour (csrc/raster.hip)
 
 Grid convention (the kernels' own): field[i, j, k] sits at origin + spacing * (i, j, k), the linear point index is
 (i * ny + j) * nz + k, and a point is inside iff field >= level.
@@ -467,6 +468,55 @@ def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT
   out = dict(texture=texture, mask=mask, uv=uv, layout=layout)
   if return_float:
     out['texture_f32'] = texture_f32
+  return out
+
+
+def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=None, near=0.05, bg=(1., 1., 1.), cull='none', supersample=1,
+                proj=None, threshold=None):
+  """The mesh dict `m` (vertices, normals, faces on the device) seen by a perspective camera, rasterised on the device
+  (ops.raster_visibility + ops.raster_shade, csrc/raster.hip; include/mnerf.h states the contract): dict(rgb [H,W,3], acc [H,W],
+  face [h,w] int32, depth [h,w], bary [h,w,3], normals [h,w,3], proj [3,4] the host matrix that was rendered) of device tensors, float32
+  unless stated.
+
+  The camera goes through `world_to_pixel`, which refuses everything but an undistorted pinhole; proj= takes a ready [3,4] matrix
+  instead (pixtocam and camtoworld are then ignored).  depth is zc, the distance the model renders along the rays of
+  camera_utils.pixels_to_rays (0 where no face is hit), acc is 1 where a face is hit: together they are what TsdfVolume.integrate takes.
+  Only surface with zc > near is seen.  face is -1, bary and normals are 0 and rgb is `bg` where nothing is hit.
+
+  The colour is `texture`: the dict `bake_texture` returns, or dict(texture [Ht,Wt,3] uint8 or float32, uv [T,3,2]) (read_ply's
+  texcoord), looked up bilinearly; or `colors` [V,3] uint8 or float32 (True: m['colors']) blended over the face; or, with neither, the
+  shaded normal 0.5 + 0.5 n.  cull = 'back' drops faces seen from behind (counter-clockwise seen from the camera is front).
+
+  supersample = k renders at h x w = k height x k width, the first two rows of the matrix scaled by k, and returns rgb and acc
+  box-averaged to [height, width] (plain torch); the GEOMETRIC buffers (face, depth, bary, normals) stay at the rendered resolution
+  [k height, k width], since averaging ids or depths across a silhouette means nothing.  A mesh without faces gives the background and
+  launches nothing.  `threshold` is ops.raster_visibility's."""
+  height, width, k = int(height), int(width), int(supersample)
+  if height < 1 or width < 1 or k < 1:
+    raise ValueError(f'render_mesh: height = {height}, width = {width} and supersample = {k} must be at least 1')
+  P = np.array(world_to_pixel(pixtocam, camtoworld) if proj is None else _host(proj, np.float32).reshape(3, 4), dtype=np.float32)
+  if k > 1:
+    P[:2] *= np.float32(k)
+  h, w = k * height, k * width
+  dm = dict(vertices=m['vertices'].contiguous(), normals=m['normals'].contiguous(), faces=m['faces'].contiguous())
+  dev = dm['vertices'].device
+  if colors is True:
+    colors = m.get('colors')
+  kw = dict(colors=None if colors is None else torch.as_tensor(colors).to(dev).contiguous())
+  if texture is not None:
+    kw.update(texture=torch.as_tensor(texture['texture']).to(dev).contiguous(), uv=torch.as_tensor(texture['uv']).to(device=dev, dtype=torch.float32).contiguous())
+  bg = [float(v) for v in bg]
+  if int(dm['faces'].shape[0]) == 0:
+    z = lambda *s, dtype=torch.float32: torch.zeros(s, dtype=dtype, device=dev)
+    out = dict(face=torch.full((h, w), -1, dtype=torch.int32, device=dev), depth=z(h, w), acc=z(h, w), bary=z(h, w, 3), normals=z(h, w, 3),
+               rgb=torch.tensor(bg, dtype=torch.float32, device=dev).expand(h, w, 3).contiguous())
+  else:
+    vis = ops.raster_visibility(dm, P, h, w, near, cull=cull, threshold=threshold)
+    out = ops.raster_shade(dm, P, vis, near, bg=bg, **kw)
+  if k > 1:
+    out['rgb'] = out['rgb'].reshape(height, k, width, k, 3).mean((1, 3))
+    out['acc'] = out['acc'].reshape(height, k, width, k).mean((1, 3))
+  out['proj'] = P
   return out
 
 

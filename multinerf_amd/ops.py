@@ -1909,3 +1909,112 @@ def atlas_uvs(m, layout):
   uv = torch.empty((int(a.n_faces), 3, 2), dtype=f32, device=keep[0].device)
   L.check(lib().mnr_atlas_uvs(C.byref(a), _ptr(uv), _stream()))
   return uv
+
+
+# ----------------------------------------------------------------------------- mesh rasteriser (csrc/raster.hip)
+
+# box pixels above which a face is rasterised by a workgroup instead of a thread: the A/B of profiles/mesh_render.md
+RASTER_THRESHOLD = 128
+
+
+def _raster_args(name, m, proj, height, width, near):
+  """(RasterArgs with the geometry set, the tensors it points to) of a mesh dict (vertices, normals, faces on the device), a [3,4]
+  projection (host array or tensor; it is passed by value) and the image size."""
+  verts, normals, faces = m['vertices'], m['normals'], m['faces']
+  _chk(verts, f32, f'{name}: vertices')
+  _chk(normals, f32, f'{name}: normals')
+  if verts.dim() != 2 or verts.shape[1] != 3 or normals.shape != verts.shape:
+    raise ValueError(f'{name}: vertices and normals must be [V,3], are {tuple(verts.shape)} and {tuple(normals.shape)}')
+  _chk(faces, torch.int32, f'{name}: faces')                 # (no index check: the kernels skip a face with an index outside the vertices)
+  if faces.dim() != 2 or faces.shape[1] != 3:
+    raise ValueError(f'{name}: faces must be [T,3], is {tuple(faces.shape)}')
+  V, T = int(verts.shape[0]), int(faces.shape[0])
+  if T >= 2 ** 31 - 1:
+    raise ValueError(f'{name}: {T} faces: must stay below 2^31 - 1 (a face id is the low word of a pixel\'s key)')
+  P = [float(v) for v in torch.as_tensor(proj).detach().cpu().reshape(-1).tolist()]
+  if len(P) != 12 or not all(math.isfinite(v) for v in P):
+    raise ValueError(f'{name}: proj must be a finite [3,4] matrix')
+  height, width, near = int(height), int(width), C.c_float(float(near)).value
+  if height < 1 or width < 1:
+    raise ValueError(f'{name}: an image of {height} x {width} pixels: both sides must be at least 1')
+  if not (near > 0. and math.isfinite(near)):
+    raise ValueError(f'{name}: near = {near} must be positive and finite in float32')
+  a = L.RasterArgs()
+  a.verts, a.normals, a.faces, a.n_verts, a.n_faces = verts.data_ptr(), normals.data_ptr(), faces.data_ptr(), V, T
+  a.proj = (C.c_float * 12)(*P)
+  a.H, a.W, a.near = height, width, near
+  return a, (verts, normals, faces)
+
+
+def raster_visibility(m, proj, height, width, near, cull='none', threshold=None, check_faces=True):
+  """vis [height,width] int64: the visibility buffer of the mesh dict `m` (vertices, normals, faces on the device) under the [3,4]
+  projection `proj` of mesh.world_to_pixel (mnr_raster_visibility; include/mnerf.h states every operation).  A pixel holds the bits
+  of the unsigned key (bits(zc) << 32) | face of the nearest face that covers its centre with zc > near (among equal depths the lowest
+  id), or all ones (-1) where there is none.  cull = 'back' drops the faces whose geometric normal faces away from the camera.
+  `threshold` (default RASTER_THRESHOLD) is the number of bounding-box pixels above which a face is rasterised by a workgroup instead
+  of a thread: 0, any value and a huge one give the same buffer bit for bit, as do two runs (integer minimum only).  Face indices
+  outside the vertices raise ValueError (one min / max read-back; check_faces=False leaves it to the kernels, which skip such
+  a face)."""
+  name = 'raster_visibility'
+  a, keep = _raster_args(name, m, proj, height, width, near)
+  if check_faces:
+    _chk_faces(name, keep[2], keep[0].shape[0])
+  if cull not in L.RASTER_CULL:
+    raise ValueError(f"{name}: cull = {cull!r} must be 'none' or 'back'")
+  threshold = RASTER_THRESHOLD if threshold is None else int(threshold)
+  if not 0 <= threshold < 2 ** 63:
+    raise ValueError(f'{name}: threshold = {threshold} must lie in 0 .. 2^63 - 1')
+  a.cull, a.threshold = L.RASTER_CULL[cull], threshold
+  dev = keep[0].device
+  vis = torch.empty((a.H, a.W), dtype=torch.int64, device=dev)
+  work = torch.empty((int(a.n_faces) + 1,), dtype=torch.int32, device=dev)        # the large-face list and, last, its counter
+  L.check(lib().mnr_raster_visibility(C.byref(a), _ptr(vis), _ptr(work), C.c_void_p(work.data_ptr() + 4 * int(a.n_faces)), _stream()))
+  return vis
+
+
+def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1., 1., 1.)):
+  """dict(face [H,W] int32, depth [H,W], acc [H,W], bary [H,W,3], normals [H,W,3], rgb [H,W,3] float32) of a visibility buffer `vis`
+  [H,W] int64 that `raster_visibility` wrote for the same mesh, projection and near (mnr_raster_shade; include/mnerf.h): the winning
+  face (-1: none), its zc, 1 where there is one, the perspective-correct barycentrics, the interpolated unit normal and the colour:
+  `colors` [V,3] uint8 or float32 blended over the face, or `texture` [Ht,Wt,3] uint8 or float32 looked up bilinearly at the blend of
+  `uv` [T,3,2] (per face corner, v = 1 the top row: what mesh.bake_texture returns), or, with neither, 0.5 + 0.5 normal.  Pixels
+  without a face get `bg`."""
+  name = 'raster_shade'
+  _chk(vis, torch.int64, f'{name}: vis')
+  if vis.dim() != 2:
+    raise ValueError(f'{name}: vis must be [H,W], is {tuple(vis.shape)}')
+  H, W = int(vis.shape[0]), int(vis.shape[1])
+  a, keep = _raster_args(name, m, proj, H, W, near)
+  V, T = int(a.n_verts), int(a.n_faces)
+  if colors is not None and texture is not None:
+    raise ValueError(f'{name}: colors and texture are both given: the colour has one source')
+  for t, label, shape in ((colors, 'colors', (V, 3)), (texture, 'texture', None)):
+    if t is None:
+      continue
+    if t.dtype not in (torch.uint8, f32):
+      raise ValueError(f'{name}: {label} must be torch.uint8 or torch.float32, is {t.dtype}')
+    _chk(t, t.dtype, f'{name}: {label}')
+    if (shape is not None and tuple(t.shape) != shape) or (shape is None and (t.dim() != 3 or t.shape[2] != 3 or min(t.shape[:2]) < 1)):
+      raise ValueError(f'{name}: {label} must be {"[V,3]" if shape else "a non-empty [Ht,Wt,3] image"}, is {tuple(t.shape)}')
+  if texture is not None:
+    _chk(uv, f32, f'{name}: uv')
+    if tuple(uv.shape) != (T, 3, 2):
+      raise ValueError(f'{name}: uv must be [{T},3,2] (three corners a face), is {tuple(uv.shape)}')
+    if max(texture.shape[:2]) > 2 ** 24:
+      raise ValueError(f'{name}: a texture of {tuple(texture.shape[:2])} texels: a side may not exceed 2^24')
+    a.texture, a.texture_u8, a.Ht, a.Wt, a.uv = texture.data_ptr(), int(texture.dtype == torch.uint8), int(texture.shape[0]), int(texture.shape[1]), uv.data_ptr()
+  elif uv is not None:
+    raise ValueError(f'{name}: uv is given without a texture')
+  if colors is not None:
+    a.colors, a.colors_u8 = colors.data_ptr(), int(colors.dtype == torch.uint8)
+  bg = [float(v) for v in bg]
+  if len(bg) != 3 or not all(math.isfinite(v) for v in bg):
+    raise ValueError(f'{name}: bg must hold 3 finite values, is {bg}')
+  a.bg = (C.c_float * 3)(*bg)
+  dev = vis.device
+  out = dict(face=torch.empty((H, W), dtype=torch.int32, device=dev), depth=torch.empty((H, W), dtype=f32, device=dev),
+             acc=torch.empty((H, W), dtype=f32, device=dev), bary=torch.empty((H, W, 3), dtype=f32, device=dev),
+             normals=torch.empty((H, W, 3), dtype=f32, device=dev), rgb=torch.empty((H, W, 3), dtype=f32, device=dev))
+  L.check(lib().mnr_raster_shade(C.byref(a), _ptr(vis), _ptr(out['face']), _ptr(out['depth']), _ptr(out['acc']), _ptr(out['bary']),
+                                 _ptr(out['normals']), _ptr(out['rgb']), _stream()))
+  return out

@@ -205,6 +205,11 @@ inline int atomicMin(int* p, int v) {
   *p = v < o ? v : o;
   return o;
 }
+inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v) {
+  const unsigned long long o = *p;
+  *p = v < o ? v : o;
+  return o;
+}
 inline float __shfl(float v, int src, int width = 64) { return hipsim::shfl(v, src, width); }
 inline float __shfl_down(float v, unsigned d, int width = 64) {
   const int l = hipsim::cur->lane;
