@@ -12,6 +12,16 @@ Under --out_dir (default: <mesh file's directory>/mesh_eval) it writes mesh_colo
 visibility and shading, bracketed by a device synchronisation).
 
   python eval_mesh.py --mesh garden.ply --gin_configs configs/360.gin --gin_bindings "Config.data_dir = '...'" --supersample 2
+
+Geometry.  With --gt_mesh FILE (a PLY mesh or point cloud, `mesh.read_ply_geometry`) the mesh is also scored against that ground truth
+by `mesh.geometry_metrics` (csrc/meshdist.hip): accuracy, completeness, Chamfer, their medians, and precision, recall and F-score at
+every threshold, printed as `name = value` and written to mesh_metric_geometry.txt (one `name value` a line), followed by the
+seconds of sampling, grid build and the two queries.  --gt_transform FILE holds the 16 numbers of the 4 x 4 matrix from the mesh's
+frame to the ground truth's; --geometry_samples, --geometry_thresholds a,b,..., --geometry_max_dist and --geometry_bbox
+x0,y0,z0,x1,y1,z1 are geometry_metrics' arguments.  --error_ply FILE writes the mesh with its vertices coloured by their distance to
+the ground truth (turbo, 0 .. the largest threshold).  --geometry_only skips the dataset and the rendering: no config is needed.
+
+  python eval_mesh.py --mesh barn.ply --geometry_only --gt_mesh Barn.ply --gt_transform Barn_trans.txt --geometry_thresholds 0.01
 """
 
 import argparse
@@ -37,7 +47,24 @@ def parse_args(argv):
   ap.add_argument('--near', type=float, default=None, help='surface nearer than this (zc) is not seen; default: Config.near')
   ap.add_argument('--bg', default='1,1,1', help='r,g,b of the pixels no face covers')
   ap.add_argument('--cull', choices=('none', 'back'), default='none')
+  ap.add_argument('--gt_mesh', default=None, help='a ground-truth PLY (mesh or point cloud): score the geometry against it')
+  ap.add_argument('--gt_transform', default=None, help='a text file of 16 numbers: the 4 x 4 matrix from the mesh\'s frame to the ground truth\'s')
+  ap.add_argument('--geometry_samples', type=int, default=1_000_000, help='surface samples a shape')
+  ap.add_argument('--geometry_thresholds', default=None, help='a,b,...: distances of precision / recall / F-score; default: from the ground truth\'s box')
+  ap.add_argument('--geometry_max_dist', type=float, default=None, help='distances are clamped to this')
+  ap.add_argument('--geometry_bbox', default=None, help='x0,y0,z0,x1,y1,z1 in the ground truth\'s frame: samples outside are dropped')
+  ap.add_argument('--geometry_only', action='store_true', help='skip the dataset and the rendering (no config needed)')
+  ap.add_argument('--error_ply', default=None, help='write the mesh coloured by its vertices\' distance to the ground truth')
   args = ap.parse_args(argv)
+  if (args.geometry_only or args.error_ply or args.gt_transform) and not args.gt_mesh:
+    raise SystemExit('eval_mesh.py: --geometry_only, --error_ply and --gt_transform need --gt_mesh')
+  try:
+    args.geometry_thresholds = None if args.geometry_thresholds is None else [float(v) for v in args.geometry_thresholds.split(',')]
+    args.geometry_bbox = None if args.geometry_bbox is None else [float(v) for v in args.geometry_bbox.split(',')]
+    if args.geometry_bbox is not None and len(args.geometry_bbox) != 6:
+      raise ValueError
+  except ValueError:
+    raise SystemExit('eval_mesh.py: --geometry_thresholds takes numbers a,b,... and --geometry_bbox six numbers x0,y0,z0,x1,y1,z1') from None
   try:
     args.bg = [float(v) for v in args.bg.split(',')]
     if len(args.bg) != 3:
@@ -66,10 +93,51 @@ def load_mesh(path, device):
   return dm, texture, colors
 
 
+def score_geometry(args, dm, out_dir):
+  """--gt_mesh: the metrics of mesh.geometry_metrics, mesh_metric_geometry.txt, the stage times and, with --error_ply, the error mesh."""
+  from multinerf_amd import vis
+  gt = mesh.read_ply_geometry(args.gt_mesh)
+  transform = None
+  if args.gt_transform:
+    transform = np.loadtxt(args.gt_transform, dtype=np.float64).reshape(-1)
+    if transform.shape != (16,):
+      raise SystemExit(f'eval_mesh.py: {args.gt_transform} must hold 16 numbers, holds {transform.shape[0]}')
+    transform = transform.reshape(4, 4)
+  print(f'{args.gt_mesh}: {len(gt["vertices"])} vertices, {len(gt["faces"])} faces' + ('' if len(gt['faces']) else ' (a point cloud)'))
+  timings = {}
+  metrics = mesh.geometry_metrics(dm, gt, n_samples=args.geometry_samples, thresholds=args.geometry_thresholds, max_dist=args.geometry_max_dist,
+                                  transform=transform, bbox=args.geometry_bbox, timings=timings)
+  for name, value in metrics.items():
+    print(f'{name} = {value:.9g}')
+  with open(os.path.join(out_dir, 'mesh_metric_geometry.txt'), 'w') as f:
+    f.write(''.join(f'{name} {value:.9g}\n' for name, value in metrics.items()))
+  print('Geometry seconds: ' + ', '.join(f'{k} {timings[k]:.4f}' for k in ('sample', 'grid', 'query')))
+  if args.error_ply:
+    verts = dm['vertices']
+    if transform is not None:
+      h = verts.double().cpu().numpy() @ transform[:3, :3].T + transform[:3, 3]
+      w = verts.double().cpu().numpy() @ transform[3, :3] + transform[3, 3]
+      verts = torch.from_numpy((h / w[:, None]).astype(np.float32)).to(verts.device)
+    d = mesh.point_mesh_distance(verts, gt, max_dist=args.geometry_max_dist)['distance']
+    top = max(float(k.split('@')[1]) for k in metrics if k.startswith('fscore@'))
+    d = d.clamp(max=top)[None].contiguous()                  # (one image row; lo = 0 would mean `automatic` to visualize_cmap)
+    rgb = vis.visualize_cmap(d, torch.ones_like(d), 'turbo', lo=float(np.finfo(np.float32).tiny), hi=top, matte_background=False)
+    rgb8 = (rgb.reshape(-1, 3).clamp(0, 1) * 255 + 0.5).to(torch.uint8)
+    mesh.write_ply(args.error_ply, dict(vertices=dm['vertices'], normals=dm['normals'], faces=dm['faces'], colors=rgb8))
+    print(f'wrote {args.error_ply}: vertex colours turbo over 0 .. {top:g}')
+
+
 def main(argv=None):
   args = parse_args(sys.argv[1:] if argv is None else argv)
   dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', '0')))
   torch.cuda.set_device(dev)
+  out_dir = args.out_dir or os.path.join(os.path.dirname(os.path.abspath(args.mesh)), 'mesh_eval')
+  if args.geometry_only:
+    dm = load_mesh(args.mesh, dev)[0]
+    print(f'{args.mesh}: {dm["vertices"].shape[0]} vertices, {dm["faces"].shape[0]} faces')
+    os.makedirs(out_dir, exist_ok=True)
+    score_geometry(args, dm, out_dir)
+    return
   config = configs.load_preset(args.preset, args.gin_bindings) if args.preset else \
       configs.load_config(args.gin_configs, args.gin_bindings, save_config=False)
   near = float(config.near if args.near is None else args.near)
@@ -79,7 +147,6 @@ def main(argv=None):
   dataset = datasets.load_dataset(args.split, config.data_dir, config, device=dev)
   camtype = 'pano' if getattr(dataset, '_render_spherical', False) else dataset.camtype
   pixtocams = mesh._host(dataset.pixtocams, np.float64)
-  out_dir = args.out_dir or os.path.join(os.path.dirname(os.path.abspath(args.mesh)), 'mesh_eval')
   os.makedirs(out_dir, exist_ok=True)
   harness = image.MetricHarness()
   quant, crop = bool(config.eval_quantize_metrics), int(config.eval_crop_borders)
@@ -106,6 +173,8 @@ def main(argv=None):
   for name, values in (('mesh_metric_psnr.txt', psnrs), ('mesh_metric_ssim.txt', ssims), ('mesh_render_times.txt', seconds)):
     with open(os.path.join(out_dir, name), 'w') as f:
       f.write(' '.join(str(v) for v in values))
+  if args.gt_mesh:
+    score_geometry(args, dm, out_dir)
 
 
 if __name__ == '__main__':

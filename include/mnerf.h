@@ -1223,6 +1223,90 @@ int mnr_raster_visibility(const mnr_raster_args* args, uint64_t* vis, int* list,
 int mnr_raster_shade(const mnr_raster_args* args, const uint64_t* vis, int* face, float* depth, float* acc, float* bary, float* normals,
                      float* rgb, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Mesh geometry: point-to-mesh distance over a uniform grid, surface sampling  (csrc/meshdist.hip)
+ * Everything is float32 in the order written unless it says float64, no contraction; tests/geometry_ref.py restates it in NumPy,
+ * every query against every face.  dot(x, y) = (x_0 y_0 + x_1 y_1) + x_2 y_2;  cross(u, v) = (u_1 v_2 - u_2 v_1, u_2 v_0 - u_0 v_2,
+ * u_0 v_1 - u_1 v_0);  min is fminf.  A face is VALID iff its three indices lie in [0, n_verts) and its nine coordinates are
+ * finite; every kernel below skips a face that is not.  A point cloud is a mesh whose faces are (i, i, i).
+ *
+ * Squared distance of a point p to a face (a, b, c):
+ *   seg(p, u, v):  uv = v - u, up = p - u, L = dot(uv, uv);  t = min(max(dot(up, uv) / L, 0), 1) if L > 0, else 0;
+ *                  e = up - t uv (the products first, then the subtractions);  dot(e, e).
+ *   d2 = min(min(seg(p, a, b), seg(p, b, c)), seg(p, c, a)).
+ *   ab = b - a, ac = c - a, n = cross(ab, ac), nn = dot(n, n).  If nn > 0, with ap = p - a, bp = p - b, cp = p - c, bc = c - b, ca = a - c:
+ *   s_0 = dot(n, cross(ab, ap)), s_1 = dot(n, cross(bc, bp)), s_2 = dot(n, cross(ca, cp));  if s_0 >= 0 and s_1 >= 0 and s_2 >= 0:
+ *   h = dot(n, ap), d2 = min(d2, (h h) / nn).
+ * Why this form and not the closest-point routine that walks the seven Voronoi regions with unguarded quotients: that one returns
+ * NaN for a face with two equal corners, is wrong by the size of the scene for three collinear corners, and differs from its own
+ * float64 evaluation by 2e-2 on slivers.  Here three equal corners are a point and collinear corners a segment without a special
+ * case, and the plane term, a lower bound of the true distance wherever it is taken, can only be taken over the prism of the face.
+ * LIMIT.  The normal of a sliver whose height is within rounding of its corners (about 1e-7 of their size) is rounding noise; for
+ * a query that lies within rounding of the plane through the sliver's long edge and that noise, the three signs can pass and
+ * (h h) / nn can then be far below the true distance.
+ *
+ * Result per query: the minimum of key = (bits(d2) << 32) | face over the ELIGIBLE faces, d2 >= 0 so its bit pattern is monotone
+ * (the rasteriser's resolve): d2 [n] float32 the smallest squared distance, face [n] int32 the lowest face id that attains it.  A
+ * face is eligible iff it is valid and d2 <= lim, lim = max_dist max_dist in float32 (max_dist > 0; +inf: every valid face; a d2
+ * that is NaN is not eligible).  No eligible face, or a query with a coordinate that is not finite: d2 = +inf, face = -1.  The
+ * result does not depend on the order of traversal, hence not on the grid: two runs, and two grids, agree bit for bit.
+ *
+ * Grid.  Cubes of side `cell` (> 0, finite) at `origin`, dims [3] cells, dims_a in [1, MNR_MESHDIST_MAX_DIM]; cell (x, y, z) has
+ * the linear index (x dims_1 + y) dims_2 + z.  A coordinate v of axis a lies in cell(v) = int(min(max(floor((v - origin_a) / cell),
+ * 0), dims_a - 1)) (the clamps as float; that function does not decrease in v).  The caller sets origin and `hi` to the
+ * per-axis minimum and maximum over the corners of the valid faces (exactly) and dims_a = cell(hi_a) + 1.
+ *   mnr_mesh_grid_count  counts[f] (int64) = the number of cells the box of face f overlaps, prod_a (cell(max_a) - cell(min_a) + 1)
+ *                        with min_a / max_a over its three corners; 0 for a face that is not valid.
+ *   mnr_mesh_grid_fill   with offsets [n_faces + 1] (int64) the exclusive scan of counts and n_pairs its last entry: face f writes
+ *                        (cell, f) into pair_cell / pair_face [n_pairs] (int32) from offsets[f] on, x outermost, z innermost; no
+ *                        atomics, nothing outside [offsets[f], min(offsets[f + 1], n_pairs)).
+ *   The caller sorts the pairs stably by cell (a cell's faces ascending) and builds cell_start [cells + 1] (int64).
+ *   mnr_mesh_distance    one thread a query; with `order` [n] (int64, or NULL) thread t serves query order[t], so that the caller
+ *                        can sort the queries by cell and still gets the results in its own order.  With q = min(max(p, origin), hi)
+ *                        per axis, g_a = (q_a - origin_a) / cell, c_a = cell(q_a), fr_a = min(max(g_a - c_a, 0), 1) and
+ *                        out2 = dot(ex, ex), ex_a = max(max(origin_a - p_a, p_a - hi_a), 0), the thread visits the Chebyshev shells
+ *                        r = 0, 1, 2, ... of cells around c (clipped to the grid), every face of every cell, and stops after shell r
+ *                        when no side of the cube of shells <= r lies inside the grid any more, or else, with m the smallest of
+ *                        fr_a over the axes with c_a - r > 0 and 1 - fr_a over those with c_a + r < dims_a - 1,
+ *                          bound = cell max((float(r) + m) - MNR_MESHDIST_MARGIN, 0),  lb2 = (out2 + bound bound) MNR_MESHDIST_SHRINK,
+ *                        when best d2 < lb2 or lb2 > lim.  csrc/meshdist.hip argues why every face not yet seen then has a
+ *                        COMPUTED d2 of at least lb2.  shells [n] (int32, or NULL) receives the number of shells visited.
+ *   cell_start entries outside [0, n_pairs], pair_face entries outside [0, n_faces), face indices outside the vertices and entries
+ *   of order outside [0, n) are skipped: no access leaves the inputs.  n == 0, or n_pairs == 0: nothing to visit, every query gets
+ *   the empty result.
+ *
+ * Sampling.  mnr_mesh_face_areas: area[f] (float64) = 0.5 sqrt(dot(n, n)), n = cross(b - a, c - a) with the float32 corners widened
+ * first; 0 for a face that is not valid.  mnr_mesh_sample, one thread a sample i of n (n < 2^31), given cum [n_faces] (float64), the
+ * caller's inclusive running sum of the areas (an input: the order of that sum is not part of the contract):
+ *   u = ((double(i) + 0.5) / double(n)) cum[n_faces - 1];  k = the first face with cum[k] > u (binary search; n_faces - 1 if none).
+ *   mix(x), uint32 arithmetic:  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16.
+ *   s = mix(seed), h_1 = mix(s + 2 i), h_2 = mix(s + (2 i + 1));  r_j = float(h_j >> 8) 2^-24 (exact).
+ *   If r_1 > 1 - r_2 (that is r_1 + r_2 > 1, evaluated without a rounding): r_1 = 1 - r_1, r_2 = 1 - r_2.
+ *   b = ((1 - r_1) - r_2, r_1, r_2) (exact, every entry in [0, 1]);  point = (b_0 a + b_1 b) + b_2 c;  face[i] = k.
+ * Stratified in the area, no square root, no rejection.  A k that names no valid face gives face -1 and the point 0.
+ * ------------------------------------------------------------------------- */
+#define MNR_MESHDIST_MAX_DIM 1024
+#define MNR_MESHDIST_MARGIN 0.03125f            /* 2^-5 of a cell */
+#define MNR_MESHDIST_SHRINK 0.9999847412109375f /* 1 - 2^-16 */
+typedef struct {
+  const float* verts;              /* [n_verts,3] */
+  const int* faces;                /* [n_faces,3] */
+  int64_t n_verts, n_faces;
+  float origin[3];
+  float hi[3];
+  float cell;
+  int dims[3];
+} mnr_meshdist_args;
+int mnr_mesh_grid_count(const mnr_meshdist_args* args, int64_t* counts, void* stream);
+int mnr_mesh_grid_fill(const mnr_meshdist_args* args, const int64_t* offsets, int64_t n_pairs, int* pair_cell, int* pair_face,
+                       void* stream);
+int mnr_mesh_distance(const mnr_meshdist_args* args, const int64_t* cell_start, const int* pair_face, int64_t n_pairs,
+                      const float* points, const int64_t* order, int64_t n, float max_dist, float* d2, int* face, int* shells,
+                      void* stream);
+int mnr_mesh_face_areas(const float* verts, int64_t n_verts, const int* faces, int64_t n_faces, double* area, void* stream);
+int mnr_mesh_sample(const float* verts, int64_t n_verts, const int* faces, int64_t n_faces, const double* cum, int64_t n,
+                    uint32_t seed, float* points, int* face, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

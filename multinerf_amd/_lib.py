@@ -248,6 +248,14 @@ class RasterArgs(C.Structure):
               ('bg', C.c_float * 3)]
 
 
+MESHDIST_MAX_DIM = 1024            # MNR_MESHDIST_MAX_DIM
+
+
+class MeshDistArgs(C.Structure):
+  _fields_ = [('verts', vp), ('faces', vp), ('n_verts', C.c_int64), ('n_faces', C.c_int64), ('origin', C.c_float * 3), ('hi', C.c_float * 3),
+              ('cell', C.c_float), ('dims', C.c_int * 3)]
+
+
 class AdamCfg(C.Structure):
   _fields_ = [('lr', C.c_float), ('b1', C.c_float), ('b2', C.c_float), ('eps', C.c_float),
               ('bias_corr1', C.c_float), ('bias_corr2', C.c_float), ('one_minus_b1', C.c_float),
@@ -353,6 +361,11 @@ _PROTOS = {
     'mnr_atlas_uvs': ([C.POINTER(AtlasArgs), vp, vp], i32),
     'mnr_raster_visibility': ([C.POINTER(RasterArgs), vp, vp, vp, vp], i32),
     'mnr_raster_shade': ([C.POINTER(RasterArgs), vp, vp, vp, vp, vp, vp, vp, vp], i32),
+    'mnr_mesh_grid_count': ([C.POINTER(MeshDistArgs), vp, vp], i32),
+    'mnr_mesh_grid_fill': ([C.POINTER(MeshDistArgs), vp, i64, vp, vp, vp], i32),
+    'mnr_mesh_distance': ([C.POINTER(MeshDistArgs), vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp], i32),
+    'mnr_mesh_face_areas': ([vp, i64, vp, i64, vp, vp], i32),
+    'mnr_mesh_sample': ([vp, i64, vp, i64, vp, i64, C.c_uint32, vp, vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

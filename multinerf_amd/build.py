@@ -24,7 +24,7 @@ INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIB = os.path.join(HERE, 'libmnerf_hip.so')
 LIB_F32 = os.path.join(HERE, 'libmnerf_hip_f32.so')
 OBJ_DIR = os.path.join(HERE, 'build')
-SOURCES = ['api.hip', 'gemm.hip', 'gemm_blk.hip', 'fused_mlp.hip', 'resample.hip', 'features.hip', 'render.hip', 'losses.hip', 'optim.hip', 'refnerf.hip', 'camera.hip', 'robust.hip', 'metrics.hip', 'vis.hip', 'raw.hip', 'ingest.hip', 'gaussians.hip', 'mesh.hip', 'tsdf.hip', 'meshclean.hip', 'atlas.hip', 'raster.hip']
+SOURCES = ['api.hip', 'gemm.hip', 'gemm_blk.hip', 'fused_mlp.hip', 'resample.hip', 'features.hip', 'render.hip', 'losses.hip', 'optim.hip', 'refnerf.hip', 'camera.hip', 'robust.hip', 'metrics.hip', 'vis.hip', 'raw.hip', 'ingest.hip', 'gaussians.hip', 'mesh.hip', 'tsdf.hip', 'meshclean.hip', 'atlas.hip', 'raster.hip', 'meshdist.hip']
 SOURCES_F32 = [s for s in SOURCES if s not in ('gemm_blk.hip', 'fused_mlp.hip')]
 F32_DEFINES = ['-DMNR_DENSE_F32=1']
 HEADERS = [os.path.join(CSRC, 'dense_f32.inc'), os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_nt_body.inc'), os.path.join(CSRC, 'gemm_tn_body.inc'), os.path.join(CSRC, 'gemm_nt_side.inc'), os.path.join(CSRC, 'ray_losses.h'), os.path.join(CSRC, 'ipe_math.h'), os.path.join(CSRC, 'ipe_encode_body.inc'), os.path.join(INCLUDE, 'mnerf.h'), os.path.join(INCLUDE, 'mnerf_debug.h')]

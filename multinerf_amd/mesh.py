@@ -12,6 +12,9 @@
   bake_texture   a texture atlas of per-face charts, every texel queried with its own footprint's Gaussian (csrc/atlas.hip)
   write_obj      OBJ + MTL + PNG of a mesh with a baked texture (write_ply takes the texture too)
   render_mesh    rasterise a mesh from a camera: face ids, depth, barycentrics, normals, colour (csrc/raster.hip)
+  sample_surface / point_mesh_distance / geometry_metrics   area-stratified surface samples, the distance of points to a mesh or
+                 point cloud, and accuracy, completeness, Chamfer and F-score against a ground truth (csrc/meshdist.hip)
+  read_ply_geometry   a tolerant PLY reader for ground-truth meshes and point clouds
 
 Grid convention (the kernels' own): field[i, j, k] sits at origin + spacing * (i, j, k), the linear point index is
 (i * ny + j) * nz + k, and a point is inside iff field >= level.
@@ -672,3 +675,232 @@ def mesh_stats(verts, faces):
   return dict(V=V, T=T, E=E, euler=V - E + T, boundary_edges=int((uses == 1).sum()), nonmanifold_edges=int((uses > 2).sum()),
               signed_volume=float(np.einsum('ij,ij->i', a, np.cross(b, c)).sum() / 6.),
               area=float(0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=-1).sum()))
+
+
+# ----------------------------------------------------------------------------- geometry metrics (csrc/meshdist.hip)
+
+def _shape(m, device='cuda'):
+  """(verts [V,3] float32, faces [T,3] int32) on the device of a mesh or point-cloud dict of tensors or host arrays; a dict without
+  `faces` (or with None) is a cloud."""
+  verts = torch.as_tensor(m['vertices']).to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+  faces = m.get('faces')
+  if faces is None:
+    return verts, torch.zeros((0, 3), dtype=torch.int32, device=verts.device)
+  return verts, torch.as_tensor(faces).to(device=device, dtype=torch.int32).reshape(-1, 3).contiguous()
+
+
+def _cloud_faces(verts):
+  """The faces (i, i, i) under which a point cloud is a mesh."""
+  return torch.arange(verts.shape[0], dtype=torch.int32, device=verts.device)[:, None].expand(-1, 3).contiguous()
+
+
+def sample_surface(m, n, seed=0):
+  """dict(points [n,3] float32, face [n] int32): n points on the surface of `m`, stratified in the area: face k gets within 2 of
+  n A_k / A of them (ops.mesh_sample; the contract is in include/mnerf.h, the areas and their running sum are float64).  Faces with an
+  index outside the vertices, a corner that is not finite or no area get none.  A mesh without faces is a point cloud: its vertices
+  come back as they are, `face` numbers them, and n is ignored."""
+  verts, faces = _shape(m)
+  if faces.shape[0] == 0:
+    return dict(points=verts, face=torch.arange(verts.shape[0], dtype=torch.int32, device=verts.device))
+  cum = torch.cumsum(ops.mesh_face_areas(verts, faces), 0)
+  points, face = ops.mesh_sample(verts, faces, cum, n, seed)
+  return dict(points=points, face=face)
+
+
+def point_mesh_distance(points, m, max_dist=None, grid=None):
+  """dict(distance [N] float32, face [N] int32): the distance of every point to the surface of `m` (a point cloud when it has no
+  faces: the distance to its nearest point) and the face (point) that attains it: sqrt of ops.point_mesh_distance's d2 in float32.
+  With `max_dist`, farther faces do not count; where none counts, distance = +inf and face = -1."""
+  verts, faces = _shape(m)
+  if faces.shape[0] == 0:
+    faces = _cloud_faces(verts)
+  points = torch.as_tensor(points).to(device=verts.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+  d2, face = ops.point_mesh_distance(points, verts, faces, max_dist=max_dist, grid=grid, check_faces=False)
+  return dict(distance=torch.sqrt(d2), face=face)
+
+
+# default thresholds of `geometry_metrics` as fractions of the ground truth's bounding-box diagonal
+GEOMETRY_THRESHOLDS = (0.0025, 0.005, 0.01)
+
+
+def geometry_metrics(pred, gt, n_samples=1_000_000, thresholds=None, max_dist=None, seed=0, transform=None, bbox=None, timings=None):
+  """Geometric error of the mesh `pred` against the ground truth `gt` (a mesh, or a point cloud: a dict without faces) as a dict of
+  Python floats.  Both surfaces are sampled (`sample_surface`, n_samples points each, seeds `seed` and `seed + 1`; a cloud is its
+  own sample); d_acc is the distance of pred's samples to gt (point to triangle, or point to point for a cloud), d_comp that of
+  gt's samples to pred (`point_mesh_distance`).
+    accuracy = mean d_acc, completeness = mean d_comp, chamfer = (accuracy + completeness) / 2 (DTU's three numbers),
+    accuracy_median, completeness_median,
+    precision@t = mean(d_acc < t), recall@t = mean(d_comp < t), fscore@t = 2 P R / (P + R), 0 when P + R = 0 (Tanks and Temples),
+    for every t of `thresholds`, written with %g; n_pred, n_gt the numbers of samples scored.
+  The reductions are torch float64 on the device.
+
+  Decisions.  `max_dist` CLAMPS the distances to it (and lets the search stop there).  DTU's evaluation drops such points instead;
+  clamping keeps a floater visible in the mean, where dropping rewards it.  `thresholds` left at None are GEOMETRY_THRESHOLDS =
+  0.25 %, 0.5 % and 1 % of the diagonal of gt's bounding box: scale-free, and of the order of the thresholds Tanks and Temples
+  publishes for its scenes (3 to 15 mm on scenes of metres); pass the benchmark's own where there are such.
+  `transform` is a 4 x 4 matrix from pred's frame to gt's, applied to pred's vertices in float64 on the host before anything else.
+  `bbox` (x0, y0, z0, x1, y1, z1) drops the samples of both shapes outside that axis-aligned box of gt's frame; the distances are
+  still taken to the whole of the other shape.  Tanks and Temples' ORIENTED crop volumes and its ICP refinement are not supported.
+  `timings`, a dict, receives the seconds of `sample`, `grid` and `query` (each bracketed by a device synchronisation)."""
+  pv, pf = _shape(pred)
+  gv, gf = _shape(gt)
+  dev = gv.device
+  if transform is not None:
+    M = np.asarray(_host(transform, np.float64)).reshape(-1)
+    if M.shape != (16,) or not np.isfinite(M).all():
+      raise ValueError('geometry_metrics: transform must be a finite 4 x 4 matrix')
+    M = M.reshape(4, 4)
+    h = _host(pv, np.float64) @ M[:3, :3].T + M[:3, 3]
+    w = _host(pv, np.float64) @ M[3, :3] + M[3, 3]
+    pv = torch.from_numpy((h / w[:, None]).astype(np.float32)).to(dev)
+  if gv.shape[0] == 0 or pv.shape[0] == 0:
+    raise ValueError('geometry_metrics: a shape without vertices')
+  if max_dist is not None and not (float(max_dist) > 0. and math.isfinite(float(max_dist))):
+    raise ValueError(f'geometry_metrics: max_dist = {max_dist} must be positive and finite')
+  if thresholds is None:
+    finite = gv[torch.isfinite(gv).all(1)].double()
+    diag = float(torch.linalg.norm(finite.max(0).values - finite.min(0).values))
+    thresholds = tuple(f * diag for f in GEOMETRY_THRESHOLDS)
+  thresholds = [float(t) for t in thresholds]
+  if not all(t > 0. and math.isfinite(t) for t in thresholds):
+    raise ValueError(f'geometry_metrics: thresholds must be positive and finite, are {thresholds}')
+  clock = {}
+
+  def timed(key, fn):
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = fn()
+    torch.cuda.synchronize()
+    clock[key] = clock.get(key, 0.) + time.time() - t0
+    return out
+
+  shapes = {'pred': (pv, pf if pf.shape[0] else None), 'gt': (gv, gf if gf.shape[0] else None)}
+  as_dict = lambda k: dict(vertices=shapes[k][0], faces=shapes[k][1])
+  samples = {k: timed('sample', lambda k=k: sample_surface(as_dict(k), n_samples, seed + (k == 'gt'))['points']) for k in shapes}
+  if bbox is not None:
+    box = [float(v) for v in bbox]
+    if len(box) != 6 or not all(math.isfinite(v) for v in box) or any(box[d] > box[d + 3] for d in range(3)):
+      raise ValueError(f'geometry_metrics: bbox must be x0, y0, z0, x1, y1, z1 with x0 <= x1 ..., is {bbox}')
+    lo, hi = torch.tensor(box[:3], device=dev), torch.tensor(box[3:], device=dev)
+    samples = {k: p[((p >= lo) & (p <= hi)).all(1)].contiguous() for k, p in samples.items()}
+  if min(p.shape[0] for p in samples.values()) == 0:
+    raise ValueError('geometry_metrics: no sample of a shape is left to score')
+  dist = {}
+  for key, src, dst in (('acc', 'pred', 'gt'), ('comp', 'gt', 'pred')):
+    v, f = shapes[dst]
+    f = _cloud_faces(v) if f is None else f
+    grid = timed('grid', lambda: ops.mesh_grid_build(v, f))
+    d2, _ = timed('query', lambda: ops.point_mesh_distance(samples[src], v, f, max_dist=max_dist, grid=grid, check_faces=False))
+    d = torch.sqrt(d2).double()
+    dist[key] = d.clamp(max=float(max_dist)) if max_dist is not None else d
+  if timings is not None:
+    timings.update(clock)
+  out = dict(accuracy=float(dist['acc'].mean()), completeness=float(dist['comp'].mean()))
+  out['chamfer'] = 0.5 * (out['accuracy'] + out['completeness'])
+  out['accuracy_median'], out['completeness_median'] = float(dist['acc'].median()), float(dist['comp'].median())
+  for t in thresholds:
+    P, R = float((dist['acc'] < t).double().mean()), float((dist['comp'] < t).double().mean())
+    out[f'precision@{t:g}'], out[f'recall@{t:g}'], out[f'fscore@{t:g}'] = P, R, (2. * P * R / (P + R) if P + R > 0. else 0.)
+  out['n_pred'], out['n_gt'] = float(samples['pred'].shape[0]), float(samples['gt'].shape[0])
+  return out
+
+
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def read_ply_geometry(path):
+  """A ground-truth PLY file, read tolerantly, as dict(vertices [V,3] float32, faces [T,3] int32 (T = 0: a point cloud), normals
+  [V,3] float32 or None, colors [V,3] uint8 or None) of host arrays.  `ascii` and `binary_little_endian`; a `vertex` element with
+  x y z as float or double, optionally nx ny nz and red green blue, and any other scalar properties, which are skipped; optionally a
+  `face` element with `list uchar|char int|uint vertex_indices|vertex_index`, further scalar properties (skipped) and the
+  `list uchar float texcoord` of `write_ply`.  Triangles only; elements after these are ignored.  Anything else raises ValueError
+  and names what it met.  (`read_ply` reads `write_ply`'s own layout and is untouched.)"""
+  with open(path, 'rb') as fh:
+    data = fh.read()
+  at = data.find(b'end_header')
+  if not data.startswith(b'ply') or at < 0:
+    raise ValueError(f'{path}: not a PLY file')
+  end = data.index(b'\n', at) + 1
+  lines = [l.strip() for l in data[:end].decode('ascii', 'replace').splitlines()]
+  fmt = next((l.split()[1] for l in lines if l.startswith('format ')), None)
+  if fmt not in ('ascii', 'binary_little_endian'):
+    raise ValueError(f'{path}: format {fmt}: only ascii and binary_little_endian are read')
+  elements = []
+  for line in lines:
+    w = line.split()
+    if w[:1] == ['element']:
+      elements.append((w[1], int(w[2]), []))
+    elif w[:1] == ['property']:
+      if not elements:
+        raise ValueError(f'{path}: a property before any element')
+      elements[-1][2].append(w[1:])
+  names = [e[0] for e in elements]
+  if 'vertex' not in names:
+    raise ValueError(f'{path}: no vertex element')
+  wanted = names[:max(names.index('vertex'), names.index('face') if 'face' in names else 0) + 1]
+  tokens = data[end:].split() if fmt == 'ascii' else None
+  pos, out = (0 if fmt == 'ascii' else end), {}
+  for name, count, props in elements[:len(wanted)]:
+    for p in props:
+      if p[0] == 'list' and (name != 'face' or p[1] not in ('uchar', 'uint8', 'char', 'int8') or p[2] not in _PLY_TYPES):
+        raise ValueError(f'{path}: element {name} has the list property `{" ".join(p)}`')
+      if p[0] != 'list' and p[0] not in _PLY_TYPES:
+        raise ValueError(f'{path}: element {name} has a property of type {p[0]}')
+    fields = []
+    for p in props:
+      if p[0] != 'list':
+        fields.append((p[1], '<' + _PLY_TYPES[p[0]]))
+        continue
+      if p[3] in ('vertex_indices', 'vertex_index'):
+        if p[2] not in ('int', 'int32', 'uint', 'uint32'):
+          raise ValueError(f'{path}: face indices of type {p[2]}')
+        length = 3
+      elif p[3] == 'texcoord':
+        length = 6
+      else:
+        raise ValueError(f'{path}: element face has the list property `{" ".join(p)}`')
+      fields += [('#' + p[3], 'u1'), (p[3], '<' + _PLY_TYPES[p[2]], (length,))]
+    dtype = np.dtype(fields)
+    width = sum(int(np.prod(f[2])) if len(f) > 2 else 1 for f in fields)
+    if fmt == 'ascii':
+      rows = tokens[pos:pos + count * width]
+      if len(rows) != count * width:
+        raise ValueError(f'{path}: element {name} ends early' + (' (only triangles are read)' if name == 'face' else ''))
+      flat = np.array(rows, dtype=np.float64).reshape(count, width)
+      rec, first = np.zeros((count,), dtype=dtype), 0
+      for f in fields:
+        k = int(np.prod(f[2])) if len(f) > 2 else 1
+        rec[f[0]] = flat[:, first] if len(f) == 2 else flat[:, first:first + k]
+        first += k
+      pos += count * width
+    else:
+      if len(data) - pos < count * dtype.itemsize:
+        if name == 'face':
+          raise ValueError(f'{path}: the face element does not hold {count} triangles (only triangles are read)')
+        raise ValueError(f'{path}: element {name} ends early')
+      rec = np.frombuffer(data, dtype=dtype, count=count, offset=pos)
+      pos += count * dtype.itemsize
+    if name == 'face':
+      key = 'vertex_indices' if 'vertex_indices' in rec.dtype.names else 'vertex_index' if 'vertex_index' in rec.dtype.names else None
+      if key is None:
+        raise ValueError(f'{path}: the face element has no vertex_indices')
+      sizes = rec['#' + key]
+      if count and (sizes != 3).any():
+        raise ValueError(f'{path}: a face with {int(sizes[sizes != 3][0])} vertices (only triangles are read)')
+    out[name] = rec
+  v = out['vertex']
+  V = len(v)
+  if not all(n in (v.dtype.names or ()) and v.dtype[n].kind == 'f' for n in ('x', 'y', 'z')):
+    raise ValueError(f'{path}: the vertex element needs x y z as float or double, has {v.dtype.names}')
+  col = lambda ns, dt: np.ascontiguousarray(np.stack([v[n] for n in ns], -1).astype(dt)) if V else np.zeros((0, 3), dtype=dt)
+  has = lambda ns: all(n in v.dtype.names for n in ns)
+  faces = np.zeros((0, 3), dtype=np.int32)
+  if 'face' in out and len(out['face']):
+    f = out['face']
+    faces = np.ascontiguousarray(f['vertex_indices' if 'vertex_indices' in f.dtype.names else 'vertex_index'].astype(np.int64))
+    if faces.min() < 0 or faces.max() >= V:
+      raise ValueError(f'{path}: face indices {faces.min()} .. {faces.max()} outside the {V} vertices')
+    faces = faces.astype(np.int32)
+  return dict(vertices=col(('x', 'y', 'z'), np.float32), faces=faces, normals=col(('nx', 'ny', 'nz'), np.float32) if has(('nx', 'ny', 'nz')) else None,
+              colors=col(('red', 'green', 'blue'), np.uint8) if has(('red', 'green', 'blue')) else None)

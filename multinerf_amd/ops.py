@@ -2018,3 +2018,191 @@ def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1.,
   L.check(lib().mnr_raster_shade(C.byref(a), _ptr(vis), _ptr(out['face']), _ptr(out['depth']), _ptr(out['acc']), _ptr(out['bary']),
                                  _ptr(out['normals']), _ptr(out['rgb']), _stream()))
   return out
+
+
+# ----------------------------------------------------------------------------- mesh geometry (csrc/meshdist.hip)
+
+# `mesh_grid_build` coarsens its cell (times 2) while the grid holds more than this many (cell, face) pairs a valid face
+MESH_GRID_PAIRS_PER_FACE = 8
+
+
+def _chk_mesh(name, verts, faces):
+  _chk(verts, f32, f'{name}: verts')
+  _chk(faces, torch.int32, f'{name}: faces')
+  if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+    raise ValueError(f'{name}: verts must be [V,3] and faces [T,3], are {tuple(verts.shape)} and {tuple(faces.shape)}')
+  V, T = int(verts.shape[0]), int(faces.shape[0])
+  if V >= 2 ** 31 or T >= 2 ** 31 - 1:
+    raise ValueError(f'{name}: {V} vertices and {T} faces: must stay below 2^31 and 2^31 - 1 (a face id is the low word of a key)')
+  return V, T
+
+
+def mesh_face_areas(verts, faces):
+  """area [T] float64 of the faces (mnr_mesh_face_areas; include/mnerf.h): 0.5 |(b - a) x (c - a)| in float64 from the float32
+  corners, 0 for a face with an index outside the vertices or a corner that is not finite."""
+  V, T = _chk_mesh('mesh_face_areas', verts, faces)
+  area = torch.empty((T,), dtype=torch.float64, device=verts.device)
+  L.check(lib().mnr_mesh_face_areas(_ptr(verts), V, _ptr(faces), T, _ptr(area), _stream()))
+  return area
+
+
+def mesh_sample(verts, faces, cum, n, seed):
+  """(points [n,3] float32, face [n] int32): n points on the surface, stratified in the area (mnr_mesh_sample; include/mnerf.h).  `cum`
+  [T] float64 is the inclusive running sum of `mesh_face_areas` (the caller's: the order of that sum is not part of the contract);
+  sample i lands on the first face whose cum exceeds (i + 0.5) / n of the total, at barycentrics from a 32-bit integer mix of
+  (seed, i).  The total must be positive and finite (one read-back)."""
+  name = 'mesh_sample'
+  V, T = _chk_mesh(name, verts, faces)
+  _chk(cum, torch.float64, f'{name}: cum')
+  if tuple(cum.shape) != (T,):
+    raise ValueError(f'{name}: cum must be [{T}], is {tuple(cum.shape)}')
+  n, seed = int(n), int(seed)
+  if not 0 <= n < 2 ** 31:
+    raise ValueError(f'{name}: n = {n} must lie in 0 .. 2^31 - 1')
+  if not 0 <= seed < 2 ** 32:
+    raise ValueError(f'{name}: seed = {seed} must lie in 0 .. 2^32 - 1')
+  points = torch.empty((n, 3), dtype=f32, device=verts.device)
+  face = torch.empty((n,), dtype=torch.int32, device=verts.device)
+  if n == 0:
+    return points, face
+  total = float(cum[-1]) if T > 0 else 0.
+  if not (total > 0. and math.isfinite(total)):
+    raise ValueError(f'{name}: the total area is {total}: there is no surface to sample')
+  L.check(lib().mnr_mesh_sample(_ptr(verts), V, _ptr(faces), T, _ptr(cum), n, seed, _ptr(points), _ptr(face), _stream()))
+  return points, face
+
+
+def _meshdist_args(verts, faces, origin, hi, cell, dims):
+  a = L.MeshDistArgs()
+  a.verts, a.faces, a.n_verts, a.n_faces = verts.data_ptr(), faces.data_ptr(), int(verts.shape[0]), int(faces.shape[0])
+  a.origin, a.hi, a.cell, a.dims = (C.c_float * 3)(*origin), (C.c_float * 3)(*hi), cell, (C.c_int * 3)(*dims)
+  return a
+
+
+def _grid_dims(origin, hi, cell):
+  """dims_a = cell(hi_a) + 1 with the kernels' float32 arithmetic (include/mnerf.h)."""
+  import numpy as np
+  o, h = np.asarray(origin, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+  return [int(v) + 1 for v in np.floor((h - o) / np.float32(cell))]
+
+
+def mesh_grid_build(verts, faces, cell=None):
+  """A uniform grid over the faces for `point_mesh_distance` (mnr_mesh_grid_count / mnr_mesh_grid_fill; include/mnerf.h): a dict of
+  origin and hi (3 floats each: the box of the corners of the valid faces), cell, dims (3 ints), cell_start [cells + 1] int64 and
+  pair_faces [pairs] int32 (cell (x, y, z), linear index (x dims[1] + y) dims[2] + z, holds pair_faces[cell_start[i] :
+  cell_start[i + 1]], ascending), n_valid and pairs.  A face is registered in every cell its axis-aligned box overlaps.
+
+  The cell, when not given (a decision, not a derived number): with e_1 >= e_2 >= e_3 the box's extents and T the number of valid
+  faces, the largest of e_1 / T, sqrt(e_1 e_2 / T) and cbrt(e_1 e_2 e_3 / T), so that the grid has about as many cells as there are
+  faces whether the box is a volume, a slab or a line (1 if all three vanish), and at least e_1 / (MAX_DIM - 1), MAX_DIM = 1024
+  cells an axis being the kernels' limit.  Then the pairs are counted (one read-back) and the cell is doubled, and the count repeated,
+  while they exceed MESH_GRID_PAIRS_PER_FACE = 8 a valid face: a few faces that span the scene must not blow the list up, and a single
+  cell ends it at one pair a face.  A given `cell` is taken as it is (ValueError if it needs more than MAX_DIM cells an axis).
+  The scan, the stable sort by cell and cell_start (bincount, cumsum) are torch on the device; the pair list is the same in every
+  run.  No valid face: a grid of one empty cell."""
+  name = 'mesh_grid_build'
+  V, T = _chk_mesh(name, verts, faces)
+  dev = verts.device
+  if cell is not None:
+    cell = C.c_float(float(cell)).value
+    if not (cell > 0. and math.isfinite(cell)):
+      raise ValueError(f'{name}: cell must be positive and finite in float32, is {cell}')
+  empty = dict(origin=[0., 0., 0.], hi=[0., 0., 0.], cell=1. if cell is None else cell, dims=[1, 1, 1], n_valid=0, pairs=0,
+               cell_start=torch.zeros((2,), dtype=torch.int64, device=dev), pair_faces=torch.zeros((0,), dtype=torch.int32, device=dev))
+  if T == 0 or V == 0:
+    return empty
+  idx = faces.long()
+  ok = ((idx >= 0) & (idx < V)).all(1)
+  corners = verts[idx.clamp(0, V - 1)]
+  ok &= torch.isfinite(corners).all(2).all(1)
+  n_valid = int(ok.sum())
+  if n_valid == 0:
+    return empty
+  corners = corners[ok].reshape(-1, 3)
+  origin, hi = corners.min(0).values.tolist(), corners.max(0).values.tolist()
+  del corners, idx
+  forced = cell is not None
+  if not forced:
+    e = sorted((h - o for o, h in zip(origin, hi)), reverse=True)
+    cell = max(e[0] / n_valid, math.sqrt(e[0] * e[1] / n_valid), (e[0] * e[1] * e[2] / n_valid) ** (1. / 3.), e[0] / (L.MESHDIST_MAX_DIM - 1))
+    cell = C.c_float(cell if cell > 0. else 1.).value
+  while True:
+    dims = _grid_dims(origin, hi, cell)
+    if max(dims) > L.MESHDIST_MAX_DIM:
+      if forced:
+        raise ValueError(f'{name}: cell = {cell:.6g} needs {dims} cells: at most {L.MESHDIST_MAX_DIM} an axis')
+      cell = C.c_float(2. * cell).value                      # (rounding of the automatic cell at the limit)
+      continue
+    a = _meshdist_args(verts, faces, origin, hi, cell, dims)
+    counts = torch.empty((T,), dtype=torch.int64, device=dev)
+    L.check(lib().mnr_mesh_grid_count(C.byref(a), _ptr(counts), _stream()))
+    offsets = torch.cat([torch.zeros((1,), dtype=torch.int64, device=dev), torch.cumsum(counts, 0)])
+    pairs = int(offsets[-1])
+    if forced or pairs <= MESH_GRID_PAIRS_PER_FACE * n_valid:
+      break
+    cell = C.c_float(2. * cell).value
+  if pairs >= 2 ** 31:
+    raise ValueError(f'{name}: cell = {cell:.6g} gives {pairs} (cell, face) pairs: must stay below 2^31')
+  pair_cell = torch.empty((pairs,), dtype=torch.int32, device=dev)
+  pair_face = torch.empty((pairs,), dtype=torch.int32, device=dev)
+  L.check(lib().mnr_mesh_grid_fill(C.byref(a), _ptr(offsets), pairs, _ptr(pair_cell), _ptr(pair_face), _stream()))
+  cells = dims[0] * dims[1] * dims[2]
+  pair_cell = pair_cell.long()
+  by_cell = torch.sort(pair_cell, stable=True).indices       # face-major list: a cell's faces stay ascending
+  cell_start = torch.cat([torch.zeros((1,), dtype=torch.int64, device=dev), torch.cumsum(torch.bincount(pair_cell, minlength=cells), 0)])
+  return dict(origin=origin, hi=hi, cell=cell, dims=dims, n_valid=n_valid, pairs=pairs, cell_start=cell_start.contiguous(),
+              pair_faces=pair_face[by_cell].contiguous())
+
+
+def point_mesh_distance(points, verts, faces, max_dist=None, grid=None, cell=None, check_faces=True, return_shells=False):
+  """(d2 [N] float32, face [N] int32): the squared distance of every point to the nearest face of the mesh and the lowest id of a
+  face that attains it (mnr_mesh_distance; include/mnerf.h states the formula, every operation in its order).  A point cloud is a
+  mesh whose faces are (i, i, i).  With `max_dist` (positive, finite) only faces with d2 <= max_dist^2 (float32) count.  Where no
+  face counts, or the point is not finite: d2 = +inf, face = -1.  The result is a minimum of (bits(d2) << 32 | face) keys over a set
+  of faces: it does not depend on the grid or the order of traversal; two runs, and two grids, agree bit for bit.
+
+  `grid` is a `mesh_grid_build` result for the same verts and faces (built here when None, with `cell` as its override).  The
+  queries are sorted by their cell (torch) so that the lanes of a wave walk the same cells; the results come back in the caller's
+  order.  Face indices outside the vertices raise ValueError (one min / max read-back; check_faces=False leaves it to the kernels,
+  which skip such a face, as they skip one with a corner that is not finite).  N = 0 or no valid face launches nothing.
+  return_shells=True appends shells [N] int32, the Chebyshev shells of cells each query visited."""
+  name = 'point_mesh_distance'
+  _chk(points, f32, f'{name}: points')
+  if points.dim() != 2 or points.shape[1] != 3:
+    raise ValueError(f'{name}: points must be [N,3], is {tuple(points.shape)}')
+  V, T = _chk_mesh(name, verts, faces)
+  if check_faces:
+    _chk_faces(name, faces, V)
+  lim = float('inf')
+  if max_dist is not None:
+    lim = C.c_float(float(max_dist)).value
+    if not (lim > 0. and math.isfinite(lim)):
+      raise ValueError(f'{name}: max_dist = {max_dist} must be positive and finite in float32')
+  if grid is not None and cell is not None:
+    raise ValueError(f'{name}: grid and cell are both given')
+  N, dev = int(points.shape[0]), points.device
+  d2 = torch.full((N,), float('inf'), dtype=f32, device=dev)
+  face = torch.full((N,), -1, dtype=torch.int32, device=dev)
+  shells = torch.zeros((N,), dtype=torch.int32, device=dev) if return_shells else None
+  out = (d2, face, shells) if return_shells else (d2, face)
+  if N == 0 or T == 0 or V == 0:
+    return out
+  if grid is None:
+    grid = mesh_grid_build(verts, faces, cell=cell)
+  cell_start, pair_faces, dims = grid['cell_start'], grid['pair_faces'], [int(v) for v in grid['dims']]
+  _chk(cell_start, torch.int64, f'{name}: grid cell_start')
+  _chk(pair_faces, torch.int32, f'{name}: grid pair_faces')
+  if len(dims) != 3 or min(dims) < 1 or tuple(cell_start.shape) != (dims[0] * dims[1] * dims[2] + 1,) or pair_faces.dim() != 1:
+    raise ValueError(f'{name}: grid: cell_start must be [{dims} cells + 1] and pair_faces a list')
+  P = int(pair_faces.shape[0])
+  if P == 0:
+    return out
+  origin, hi = [float(v) for v in grid['origin']], [float(v) for v in grid['hi']]
+  a = _meshdist_args(verts, faces, origin, hi, C.c_float(float(grid['cell'])).value, dims)
+  o, h = torch.tensor(origin, dtype=f32, device=dev), torch.tensor(hi, dtype=f32, device=dev)
+  g = torch.nan_to_num(((torch.minimum(torch.maximum(points, o), h) - o) / a.cell).floor(), nan=0.)
+  g = torch.minimum(g.clamp(min=0.), torch.tensor([d - 1 for d in dims], dtype=f32, device=dev)).long()
+  order = torch.sort((g[:, 0] * dims[1] + g[:, 1]) * dims[2] + g[:, 2]).indices.contiguous()
+  L.check(lib().mnr_mesh_distance(C.byref(a), _ptr(cell_start), _ptr(pair_faces), P, _ptr(points), _ptr(order), N, lim, _ptr(d2), _ptr(face),
+                                  _ptr(shells), _stream()))
+  return out
