@@ -13,6 +13,7 @@ of it.  It exists for parity against the plain fp32 oracle and is never on bench
 """
 
 import concurrent.futures
+import glob
 import hashlib
 import os
 import subprocess
@@ -27,7 +28,8 @@ OBJ_DIR = os.path.join(HERE, 'build')
 SOURCES = ['api.hip', 'gemm.hip', 'gemm_blk.hip', 'fused_mlp.hip', 'resample.hip', 'features.hip', 'render.hip', 'losses.hip', 'optim.hip', 'refnerf.hip', 'camera.hip', 'robust.hip', 'metrics.hip', 'vis.hip', 'raw.hip', 'ingest.hip', 'gaussians.hip', 'mesh.hip', 'tsdf.hip', 'meshclean.hip', 'atlas.hip', 'raster.hip', 'meshdist.hip']
 SOURCES_F32 = [s for s in SOURCES if s not in ('gemm_blk.hip', 'fused_mlp.hip')]
 F32_DEFINES = ['-DMNR_DENSE_F32=1']
-HEADERS = [os.path.join(CSRC, 'dense_f32.inc'), os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_nt_body.inc'), os.path.join(CSRC, 'gemm_tn_body.inc'), os.path.join(CSRC, 'gemm_nt_side.inc'), os.path.join(CSRC, 'ray_losses.h'), os.path.join(CSRC, 'ipe_math.h'), os.path.join(CSRC, 'ipe_encode_body.inc'), os.path.join(INCLUDE, 'mnerf.h'), os.path.join(INCLUDE, 'mnerf_debug.h')]
+# everything a translation unit can include: found, not listed, so that a new header cannot leave a stale library looking fresh
+HEADERS = sorted(glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(CSRC, '*.inc'))) + sorted(glob.glob(os.path.join(INCLUDE, '*.h')))
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function'] + os.environ.get('MNR_EXTRA_HIPCC_FLAGS', '').split()
 
 
@@ -36,6 +38,14 @@ def _hipcc():
     if c and (os.path.isabs(c) and os.path.exists(c) or not os.path.isabs(c)):
       return c
   raise RuntimeError('hipcc not found')
+
+
+def pool_size(n_jobs):
+  """Compiler processes to run at once: MAX_JOBS where the environment sets it (a machine that grants fewer CPUs than it shows),
+  else one a job up to the CPU count.  The one sizing of this build, tools/hipsim/build.py and tools/isa_report.py."""
+  if os.environ.get('MAX_JOBS'):
+    return max(1, int(os.environ['MAX_JOBS']))
+  return max(1, min(n_jobs, os.cpu_count() or 4))
 
 
 def _digest():
@@ -76,7 +86,7 @@ def build(force=False, verbose=True):
     return obj
 
   jobs = [(s, False) for s in SOURCES] + [(s, True) for s in SOURCES_F32]
-  with concurrent.futures.ThreadPoolExecutor(max_workers=min(len(jobs), 2 * (os.cpu_count() or 4))) as ex:
+  with concurrent.futures.ThreadPoolExecutor(max_workers=pool_size(len(jobs))) as ex:
     objs = list(ex.map(compile_one, jobs))
   for lib, mine in ((LIB, objs[:len(SOURCES)]), (LIB_F32, objs[len(SOURCES):])):
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib] + mine

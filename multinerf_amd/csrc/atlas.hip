@@ -10,7 +10,7 @@
 //   uvs      a thread a face, 6 floats.
 // The sample kernel and the UV kernel are inverses of each other: both take a face's anchor texel and step from atlas_chart_of.
 // Every index read from faces is checked against [0, n_verts) before it is used as one.
-#include "common.h"
+#include "mesh_math.h"                                      // (brings common.h)
 
 #pragma clang fp contract(off)
 
@@ -56,17 +56,6 @@ __host__ __device__ __forceinline__ atlas_texel atlas_texel_of(int64_t s, int c,
   return t;
 }
 
-__device__ __forceinline__ bool at_finite(float x) { return x - x == 0.f; }
-
-__device__ __forceinline__ bool at_normalise(float* n) {
-  const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
-  if (!(len > 0.f && len <= MNR_F32_MAX)) return false;
-  n[0] = n[0] / len;
-  n[1] = n[1] / len;
-  n[2] = n[2] / len;
-  return true;
-}
-
 __global__ __launch_bounds__(AT_THREADS) void atlas_samples_kernel(mnr_atlas_args a, int64_t s0, int64_t n, float* __restrict__ means,
                                                                    float* __restrict__ covs, float* __restrict__ normals,
                                                                    float* __restrict__ viewdirs, int* __restrict__ face) {
@@ -77,7 +66,7 @@ __global__ __launch_bounds__(AT_THREADS) void atlas_samples_kernel(mnr_atlas_arg
   int owner = -1;
   bool valid = tx.face < a.n_faces;
   int id[3] = {0, 0, 0};
-  if (valid) {
+  if (valid) {                                              // (written out: mesh_face_ids and mesh_cross give this kernel other device code)
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       id[k] = a.faces[3 * tx.face + k];
@@ -93,7 +82,7 @@ __global__ __launch_bounds__(AT_THREADS) void atlas_samples_kernel(mnr_atlas_arg
       for (int d = 0; d < 3; ++d) {
         v[k][d] = a.verts[3 * (int64_t)id[k] + d];
         vn[k][d] = a.normals[3 * (int64_t)id[k] + d];
-        valid = valid && at_finite(v[k][d]);
+        valid = valid && mesh_finite(v[k][d]);
       }
     }
     const float den = (float)(a.c - 2);
@@ -123,12 +112,12 @@ __global__ __launch_bounds__(AT_THREADS) void atlas_samples_kernel(mnr_atlas_arg
       float nn[3];
 #pragma unroll
       for (int d = 0; d < 3; ++d) nn[d] = (b0 * vn[0][d] + b1 * vn[1][d]) + b2 * vn[2][d];
-      bool unit = at_normalise(nn);
+      bool unit = mesh_normalise(nn);
       if (!unit) {
         nn[0] = e1[1] * e2[2] - e1[2] * e2[1];
         nn[1] = e1[2] * e2[0] - e1[0] * e2[2];
         nn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-        unit = at_normalise(nn);
+        unit = mesh_normalise(nn);
       }
       if (unit) {
 #pragma unroll

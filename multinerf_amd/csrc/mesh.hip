@@ -33,7 +33,7 @@
 // v(b,d), v(b,c) split along q0-q2.  Seen from outside (the low-field side) the listed order is counter-clockwise iff
 //   sign(a, b, c) * (-1)^l > 0 (one inside), < 0 (three inside),   sign(a, b, c) * sign of (a, b, c, d) as a permutation > 0 (two),
 // because det(p1 - p0, p2 - p0, p3 - p0) = det(e_a, e_b, e_c); otherwise each triangle is written with its last two ids swapped.
-#include "common.h"
+#include "mesh_math.h"                                      // (brings common.h)
 
 #pragma clang fp contract(off)
 
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_emit_vertices_kernel(mnr_mt_arg
       a.verts[id * 3 + d] = P0[d] + t * (P1 - P0[d]);
       g[d] = g0[d] + t * (g1[d] - g0[d]);
     }
-    const float len = sqrtf(g[0] * g[0] + g[1] * g[1] + g[2] * g[2]);
+    const float len = sqrtf(mesh_dot(g, g));
     const bool ok = len > 0.f && len <= MNR_F32_MAX;
 #pragma unroll
     for (int d = 0; d < 3; ++d) a.normals[id * 3 + d] = ok ? -g[d] / len : 0.f;
@@ -312,7 +312,7 @@ static int mt_check_grid(const mnr_mt_args* a, const char* who, int64_t* n_point
   MNR_CHECK_ARG(a->spacing > 0.f && a->spacing <= MNR_F32_MAX, "%s: the spacing must be positive and finite, is %g", who,
                 (double)a->spacing);
   for (int d = 0; d < 3; ++d)
-    MNR_CHECK_ARG(a->origin[d] - a->origin[d] == 0.f, "%s: the origin must be finite", who);
+    MNR_CHECK_ARG(mesh_finite(a->origin[d]), "%s: the origin must be finite", who);
   return MNR_OK;
 }
 

@@ -21,7 +21,7 @@
 // grid spacings has about 4 members and 20 faces, so a wave a cluster would idle most lanes; a thread a cluster gathers
 // float32 triples through the lists (uncoalesced, L2-resident: a mesh is a few tens of MB) and is bound by those gathers, not
 // by the float64 arithmetic.  faces: one thread a face.
-#include "common.h"
+#include "mesh_math.h"                                      // (brings common.h)
 
 #pragma clang fp contract(off)
 
@@ -42,11 +42,7 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_cc_hook_kernel(const int* __r
   const int64_t f = (int64_t)blockIdx.x * MC_THREADS + threadIdx.x;
   if (f >= T) return;
   int x[3], l[3];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    x[s] = faces[3 * f + s];
-    if (x[s] < 0 || x[s] >= V) return;
-  }
+  if (!mesh_face_ids(faces, f, V, x)) return;
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
     l[s] = labels[x[s]];
@@ -118,7 +114,7 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_cluster_keys_kernel(const flo
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const float x = verts[3 * v + a];
-    finite = finite && (x - x == 0.f);
+    finite = finite && mesh_finite(x);
     const float q = floorf((x - g.o[a]) / g.cell);
     const bool ok = q >= 0.f && q < (float)MNR_MESH_CELL_LIMIT;
     inside = inside && ok;
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_cluster_keys_kernel(const flo
 
 static int mc_check_grid(const char* name, const float* origin, float cell) {
   MNR_CHECK_ARG(origin, "%s: needs origin [3] (host)", name);
-  for (int d = 0; d < 3; ++d) MNR_CHECK_ARG(origin[d] - origin[d] == 0.f, "%s: the origin must be finite", name);
+  for (int d = 0; d < 3; ++d) MNR_CHECK_ARG(mesh_finite(origin[d]), "%s: the origin must be finite", name);
   MNR_CHECK_ARG(cell > 0.f && cell <= MNR_F32_MAX, "%s: cell must be positive and finite, is %g", name, (double)cell);
   return MNR_OK;
 }
@@ -150,8 +146,6 @@ extern "C" int mnr_mesh_cluster_keys(const float* verts, int64_t n_verts, const 
 }
 
 // ---- vertex clustering: per-cluster accumulate, solve, attributes
-
-__device__ __forceinline__ bool mc_finite(double x) { return x - x == 0.0; }
 
 template <bool COLOR>
 __global__ __launch_bounds__(MC_THREADS) void mesh_cluster_solve_kernel(mnr_mesh_cluster_args a) {
@@ -196,8 +190,8 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_cluster_solve_kernel(mnr_mesh
     const int f = a.cluster_faces[n];
     if (f < 0 || f >= a.n_faces) continue;
     const int ia = a.faces[3 * (int64_t)f], ib = a.faces[3 * (int64_t)f + 1], ic = a.faces[3 * (int64_t)f + 2];
-    if (ia < 0 || ia >= a.n_verts || ib < 0 || ib >= a.n_verts || ic < 0 || ic >= a.n_verts) continue;
-    double pa[3], e1[3], e2[3];
+    if (ia < 0 || ia >= a.n_verts || ib < 0 || ib >= a.n_verts || ic < 0 || ic >= a.n_verts) continue;      // (mesh_face_ids gives other device code here)
+    double pa[3], e1[3], e2[3], nf[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       pa[c] = (double)a.verts[3 * (int64_t)ia + c] - m[c];
@@ -205,10 +199,11 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_cluster_solve_kernel(mnr_mesh
       e1[c] = pb - pa[c];
       e2[c] = pc - pa[c];
     }
-    const double n0 = e1[1] * e2[2] - e1[2] * e2[1], n1 = e1[2] * e2[0] - e1[0] * e2[2], n2 = e1[0] * e2[1] - e1[1] * e2[0];
-    const double L = sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+    mesh_cross(e1, e2, nf);
+    const double n0 = nf[0], n1 = nf[1], n2 = nf[2];
+    const double L = sqrt(mesh_dot(nf, nf));
     if (!(L > 0. && L < MC_INF)) continue;
-    const double d = (n0 * pa[0] + n1 * pa[1]) + n2 * pa[2];
+    const double d = mesh_dot(nf, pa);
     A00 += (n0 * n0) / L;
     A01 += (n0 * n1) / L;
     A02 += (n0 * n2) / L;
@@ -233,9 +228,9 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_cluster_solve_kernel(mnr_mesh
   x[1] = ((c01 * b0 + c11 * b1) + c12 * b2) / det;
   x[2] = ((c02 * b0 + c12 * b1) + c22 * b2) / det;
   const double half = cell / 2.0;
-  const bool take = tr > 0. && mc_finite(x[0]) && mc_finite(x[1]) && mc_finite(x[2]) && fabs(x[0]) <= half && fabs(x[1]) <= half &&
+  const bool take = tr > 0. && mesh_finite(x[0]) && mesh_finite(x[1]) && mesh_finite(x[2]) && fabs(x[0]) <= half && fabs(x[1]) <= half &&
                     fabs(x[2]) <= half;
-  const double len = sqrt((sn[0] * sn[0] + sn[1] * sn[1]) + sn[2] * sn[2]);
+  const double len = sqrt(mesh_dot(sn, sn));
   const bool unit = len > 0. && len < MC_INF;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {

@@ -31,64 +31,48 @@
 // What the margin does NOT cover is the LIMIT of include/mnerf.h (a sliver whose normal is rounding noise can compute a d2 far below
 // its true distance): such a face is found when it lies in a visited cell and not otherwise.  tests/test_gpu_geometry.py holds
 // the rule: automatic, single-cell, fine and flat grids against the brute-force restatement, bit for bit.
-#include "common.h"
+#include "mesh_math.h"                                      // (brings common.h)
 
 #pragma clang fp contract(off)
 
 #define MD_THREADS 256
 #define MD_NONE 0x7f800000ffffffffull                       // (bits(+inf) << 32) | all ones: d2 = +inf, face = -1
 
-__host__ __device__ __forceinline__ bool md_finite(float x) { return x - x == 0.f; }
-
-__host__ __device__ __forceinline__ float md_dot(const float* x, const float* y) { return (x[0] * y[0] + x[1] * y[1]) + x[2] * y[2]; }
-
-__host__ __device__ __forceinline__ void md_cross(const float* u, const float* v, float* o) {
-  o[0] = u[1] * v[2] - u[2] * v[1];
-  o[1] = u[2] * v[0] - u[0] * v[2];
-  o[2] = u[0] * v[1] - u[1] * v[0];
-}
-
-__host__ __device__ __forceinline__ void md_sub(const float* x, const float* y, float* o) {
-  o[0] = x[0] - y[0];
-  o[1] = x[1] - y[1];
-  o[2] = x[2] - y[2];
-}
-
 __host__ __device__ __forceinline__ float md_seg(const float* p, const float* u, const float* v) {
   float uv[3], up[3], e[3];
-  md_sub(v, u, uv);
-  md_sub(p, u, up);
-  const float L = md_dot(uv, uv);
+  mesh_sub(v, u, uv);
+  mesh_sub(p, u, up);
+  const float L = mesh_dot(uv, uv);
   float t = 0.f;
-  if (L > 0.f) t = fminf(fmaxf(md_dot(up, uv) / L, 0.f), 1.f);
+  if (L > 0.f) t = fminf(fmaxf(mesh_dot(up, uv) / L, 0.f), 1.f);
 #pragma unroll
   for (int d = 0; d < 3; ++d) e[d] = up[d] - t * uv[d];
-  return md_dot(e, e);
+  return mesh_dot(e, e);
 }
 
 // the squared distance of include/mnerf.h
 __host__ __device__ __forceinline__ float md_d2(const float* p, const float* a, const float* b, const float* c) {
   float d2 = fminf(fminf(md_seg(p, a, b), md_seg(p, b, c)), md_seg(p, c, a));
   float ab[3], ac[3], n[3];
-  md_sub(b, a, ab);
-  md_sub(c, a, ac);
-  md_cross(ab, ac, n);
-  const float nn = md_dot(n, n);
+  mesh_sub(b, a, ab);
+  mesh_sub(c, a, ac);
+  mesh_cross(ab, ac, n);
+  const float nn = mesh_dot(n, n);
   if (nn > 0.f) {
     float ap[3], bp[3], cp[3], bc[3], ca[3], x[3];
-    md_sub(p, a, ap);
-    md_sub(p, b, bp);
-    md_sub(p, c, cp);
-    md_sub(c, b, bc);
-    md_sub(a, c, ca);
-    md_cross(ab, ap, x);
-    const float s0 = md_dot(n, x);
-    md_cross(bc, bp, x);
-    const float s1 = md_dot(n, x);
-    md_cross(ca, cp, x);
-    const float s2 = md_dot(n, x);
+    mesh_sub(p, a, ap);
+    mesh_sub(p, b, bp);
+    mesh_sub(p, c, cp);
+    mesh_sub(c, b, bc);
+    mesh_sub(a, c, ca);
+    mesh_cross(ab, ap, x);
+    const float s0 = mesh_dot(n, x);
+    mesh_cross(bc, bp, x);
+    const float s1 = mesh_dot(n, x);
+    mesh_cross(ca, cp, x);
+    const float s2 = mesh_dot(n, x);
     if (s0 >= 0.f && s1 >= 0.f && s2 >= 0.f) {
-      const float h = md_dot(n, ap);
+      const float h = mesh_dot(n, ap);
       d2 = fminf(d2, (h * h) / nn);
     }
   }
@@ -99,18 +83,14 @@ __host__ __device__ __forceinline__ float md_d2(const float* p, const float* a, 
 __device__ __forceinline__ bool md_load(const float* __restrict__ verts, int64_t n_verts, const int* __restrict__ faces, int64_t f, float* a,
                                         float* b, float* c) {
   int id[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    id[k] = faces[3 * f + k];
-    if (id[k] < 0 || id[k] >= n_verts) return false;
-  }
+  if (!mesh_face_ids(faces, f, n_verts, id)) return false;
   bool ok = true;
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     a[d] = verts[3 * (int64_t)id[0] + d];
     b[d] = verts[3 * (int64_t)id[1] + d];
     c[d] = verts[3 * (int64_t)id[2] + d];
-    ok = ok && md_finite(a[d]) && md_finite(b[d]) && md_finite(c[d]);
+    ok = ok && mesh_finite(a[d]) && mesh_finite(b[d]) && mesh_finite(c[d]);
   }
   return ok;
 }
@@ -195,7 +175,7 @@ __global__ __launch_bounds__(MD_THREADS) void meshdist_query_kernel(mnr_meshdist
   const float p[3] = {points[3 * q], points[3 * q + 1], points[3 * q + 2]};
   unsigned long long best = MD_NONE;
   int walked = 0;
-  if (n_pairs > 0 && md_finite(p[0]) && md_finite(p[1]) && md_finite(p[2])) {
+  if (n_pairs > 0 && mesh_finite(p[0]) && mesh_finite(p[1]) && mesh_finite(p[2])) {
     int c[3];
     float fr[3], ex[3];
 #pragma unroll
@@ -207,7 +187,7 @@ __global__ __launch_bounds__(MD_THREADS) void meshdist_query_kernel(mnr_meshdist
       fr[d] = fminf(fmaxf(gd - cf, 0.f), 1.f);
       ex[d] = fmaxf(fmaxf(g.origin[d] - p[d], p[d] - g.hi[d]), 0.f);
     }
-    const float out2 = md_dot(ex, ex);
+    const float out2 = mesh_dot(ex, ex);
     for (int r = 0;; ++r) {
       const int x0 = max(c[0] - r, 0), x1 = min(c[0] + r, g.dims[0] - 1);
       const int y0 = max(c[1] - r, 0), y1 = min(c[1] + r, g.dims[1] - 1);
@@ -249,14 +229,14 @@ __global__ __launch_bounds__(MD_THREADS) void meshdist_areas_kernel(const float*
   float a[3], b[3], c[3];
   double out = 0.;
   if (md_load(verts, n_verts, faces, f, a, b, c)) {
-    double u[3], v[3];
+    double u[3], v[3], n[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       u[d] = (double)b[d] - (double)a[d];
       v[d] = (double)c[d] - (double)a[d];
     }
-    const double n0 = u[1] * v[2] - u[2] * v[1], n1 = u[2] * v[0] - u[0] * v[2], n2 = u[0] * v[1] - u[1] * v[0];
-    out = 0.5 * sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+    mesh_cross(u, v, n);
+    out = 0.5 * sqrt(mesh_dot(n, n));
   }
   area[f] = out;
 }
@@ -307,7 +287,7 @@ static int md_check_grid(const char* name, const mnr_meshdist_args* g) {
   if (st != MNR_OK) return st;
   MNR_CHECK_ARG(g->cell > 0.f && g->cell <= MNR_F32_MAX, "%s: cell = %g must be positive and finite", name, (double)g->cell);
   for (int d = 0; d < 3; ++d) {
-    MNR_CHECK_ARG(g->origin[d] - g->origin[d] == 0.f && g->hi[d] - g->hi[d] == 0.f && g->origin[d] <= g->hi[d],
+    MNR_CHECK_ARG(mesh_finite(g->origin[d]) && mesh_finite(g->hi[d]) && g->origin[d] <= g->hi[d],
                   "%s: origin and hi must be finite with origin <= hi, are %g and %g on axis %d", name, (double)g->origin[d], (double)g->hi[d], d);
     MNR_CHECK_ARG(g->dims[d] >= 1 && g->dims[d] <= MNR_MESHDIST_MAX_DIM, "%s: dims[%d] = %d must lie in 1 .. %d", name, d, g->dims[d],
                   MNR_MESHDIST_MAX_DIM);

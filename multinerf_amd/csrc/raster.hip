@@ -11,7 +11,7 @@
 // The resolve is atomicMin on a 64-bit key (depth bits << 32 | face): an integer minimum does not depend on the order of arrival,
 // so two runs agree bit for bit; there is no floating-point atomic.  The list's ORDER does depend on arrival, its content and the
 // minimum do not.  Every index read from faces, the list and the buffer is checked before it is used as one.
-#include "common.h"
+#include "mesh_math.h"                                      // (brings common.h)
 
 #pragma clang fp contract(off)
 
@@ -26,18 +26,12 @@ struct rs_face {
   float s;                                                  // +1 or -1
 };
 
-__host__ __device__ __forceinline__ bool rs_finite(float x) { return x - x == 0.f; }
-
 __host__ __device__ __forceinline__ bool rs_tie(const float* a) { return a[0] > 0.f || (a[0] == 0.f && (a[1] > 0.f || (a[1] == 0.f && a[2] > 0.f))); }
 
 // false: the face is skipped (an index outside the vertices, a homogeneous coordinate that is not finite, det 0 or not finite)
 __host__ __device__ __forceinline__ bool rs_setup(const mnr_raster_args& a, int64_t f, rs_face& o) {
   int id[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    id[k] = a.faces[3 * f + k];
-    if (id[k] < 0 || id[k] >= a.n_verts) return false;
-  }
+  if (!mesh_face_ids(a.faces, f, a.n_verts, id)) return false;
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -45,21 +39,15 @@ __host__ __device__ __forceinline__ bool rs_setup(const mnr_raster_args& a, int6
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       o.h[k][r] = ((a.proj[4 * r] * x + a.proj[4 * r + 1] * y) + a.proj[4 * r + 2] * z) + a.proj[4 * r + 3];
-      ok = ok && rs_finite(o.h[k][r]);
+      ok = ok && mesh_finite(o.h[k][r]);
     }
   }
   if (!ok) return false;
   float n[3][3];
 #pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const float* p = o.h[(i + 1) % 3];
-    const float* q = o.h[(i + 2) % 3];
-    n[i][0] = p[1] * q[2] - p[2] * q[1];
-    n[i][1] = p[2] * q[0] - p[0] * q[2];
-    n[i][2] = p[0] * q[1] - p[1] * q[0];
-  }
-  const float det = (n[0][0] * o.h[0][0] + n[0][1] * o.h[0][1]) + n[0][2] * o.h[0][2];
-  if (!rs_finite(det) || det == 0.f) return false;
+  for (int i = 0; i < 3; ++i) mesh_cross(o.h[(i + 1) % 3], o.h[(i + 2) % 3], n[i]);
+  const float det = mesh_dot(n[0], o.h[0]);
+  if (!mesh_finite(det) || det == 0.f) return false;
   o.s = det > 0.f ? 1.f : -1.f;
   o.adet = fabsf(det);
 #pragma unroll
@@ -81,7 +69,7 @@ __host__ __device__ __forceinline__ bool rs_cover(const rs_face& fc, int x, int 
   }
   *S = (E[0] + E[1]) + E[2];
   *zc = fc.adet / *S;
-  return in && *S > 0.f && rs_finite(*zc) && *zc > near;
+  return in && *S > 0.f && mesh_finite(*zc) && *zc > near;
 }
 
 // the face's pixel box [x0, x1] x [y0, y1], a clause of the coverage test (include/mnerf.h): both kernels visit these pixels only; false: none
@@ -158,15 +146,6 @@ __global__ __launch_bounds__(RS_THREADS) void raster_large_kernel(mnr_raster_arg
   }
 }
 
-__device__ __forceinline__ bool rs_normalise(float* n) {
-  const float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
-  if (!(len > 0.f && len <= MNR_F32_MAX)) return false;
-  n[0] = n[0] / len;
-  n[1] = n[1] / len;
-  n[2] = n[2] / len;
-  return true;
-}
-
 __device__ __forceinline__ float rs_texel(const mnr_raster_args& a, int x, int y, int d) {
   const int64_t at = 3 * ((int64_t)y * a.Wt + x) + d;
   return a.texture_u8 ? (float)((const unsigned char*)a.texture)[at] / 255.f : ((const float*)a.texture)[at];
@@ -196,18 +175,13 @@ __global__ __launch_bounds__(RS_THREADS) void raster_shade_kernel(mnr_raster_arg
     }
 #pragma unroll
     for (int d = 0; d < 3; ++d) nrm[d] = (l[0] * vn[0][d] + l[1] * vn[1][d]) + l[2] * vn[2][d];
-    bool unit = rs_normalise(nrm);
+    bool unit = mesh_normalise(nrm);
     if (!unit) {
       float e1[3], e2[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        e1[d] = a.verts[3 * (int64_t)id[1] + d] - a.verts[3 * (int64_t)id[0] + d];
-        e2[d] = a.verts[3 * (int64_t)id[2] + d] - a.verts[3 * (int64_t)id[0] + d];
-      }
-      nrm[0] = e1[1] * e2[2] - e1[2] * e2[1];
-      nrm[1] = e1[2] * e2[0] - e1[0] * e2[2];
-      nrm[2] = e1[0] * e2[1] - e1[1] * e2[0];
-      unit = rs_normalise(nrm);
+      mesh_sub(a.verts + 3 * (int64_t)id[1], a.verts + 3 * (int64_t)id[0], e1);
+      mesh_sub(a.verts + 3 * (int64_t)id[2], a.verts + 3 * (int64_t)id[0], e2);
+      mesh_cross(e1, e2, nrm);
+      unit = mesh_normalise(nrm);
     }
     if (!unit) nrm[0] = 0.f, nrm[1] = 0.f, nrm[2] = 1.f;
     if (a.colors != nullptr) {

@@ -34,7 +34,7 @@
 //
 // mnr_mt_vertex_valid.  keep[id] = both ends of vertex id's grid edge are valid, from mesh.hip's mask / base: the id of edge
 // (p, e) is base[p] + popcount(mask[p] & ((1 << e) - 1)).  ops.marching_tetrahedra(valid=...) compacts with it.
-#include "common.h"
+#include "mesh_math.h"                                      // (brings common.h)
 
 #pragma clang fp contract(off)
 
@@ -153,7 +153,7 @@ extern "C" int mnr_tsdf_integrate(const mnr_tsdf_args* a, void* stream) {
   MNR_CHECK_ARG(a->spacing > 0.f && a->spacing <= MNR_F32_MAX, "mnr_tsdf_integrate: the spacing must be positive and finite, is %g",
                 (double)a->spacing);
   MNR_CHECK_ARG(a->trunc > 0.f && a->trunc <= MNR_F32_MAX, "mnr_tsdf_integrate: trunc must be positive and finite, is %g", (double)a->trunc);
-  for (int d = 0; d < 3; ++d) MNR_CHECK_ARG(a->origin[d] - a->origin[d] == 0.f, "mnr_tsdf_integrate: the origin must be finite");
+  for (int d = 0; d < 3; ++d) MNR_CHECK_ARG(mesh_finite(a->origin[d]), "mnr_tsdf_integrate: the origin must be finite");
   MNR_CHECK_ARG(a->F >= 0, "mnr_tsdf_integrate: F = %d frames", a->F);
   MNR_CHECK_ARG(a->H >= 1 && a->W >= 1 && a->H <= (1 << 24) && a->W <= (1 << 24),
                 "mnr_tsdf_integrate: images of [%d, %d]: both sides must lie in 1 .. 2^24", a->H, a->W);

@@ -359,9 +359,7 @@ def simplify(m, cell, origin=None, return_map=False):
   colors = None if colors is None else colors.contiguous()
   dev = verts.device
   V, T = int(verts.shape[0]), int(faces.shape[0])
-  cell = float(np.float32(cell)) if math.isfinite(float(cell)) else float(cell)
-  if not (cell > 0. and math.isfinite(cell)):
-    raise ValueError(f'simplify: cell = {cell} must be positive and finite')
+  cell = ops.positive_f32('simplify', 'cell', cell)
   if V == 0:
     out = dict(vertices=verts.clone(), normals=normals.clone(), faces=torch.zeros((0, 3), dtype=torch.int32, device=dev),
                colors=None if colors is None else colors.clone())
@@ -409,6 +407,11 @@ def simplify(m, cell, origin=None, return_map=False):
   return out
 
 
+def _device_mesh(m):
+  """The geometry of the mesh dict `m` as the contiguous tensors the ops wrappers take."""
+  return dict(vertices=m['vertices'].contiguous(), normals=m['normals'].contiguous(), faces=m['faces'].contiguous())
+
+
 def _model_color_fn(model):
   """The `color_fn` of `bake_texture` for a model: the NeRF MLP's rgb at the samples' Gaussians, with a zero GLO vector."""
   plan = model.nerf_plan
@@ -453,11 +456,11 @@ def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT
   chunk = int(chunk)
   if chunk < 1:
     raise ValueError(f'bake_texture: chunk = {chunk} must be positive')
-  m = dict(vertices=m['vertices'].contiguous(), normals=m['normals'].contiguous(), faces=m['faces'].contiguous())
+  m = _device_mesh(m)
   dev = m['vertices'].device
   T = int(m['faces'].shape[0])
   layout = ops.atlas_layout(T, cell, cols)
-  ops._chk_faces('bake_texture', m['faces'], m['vertices'].shape[0])           # once, not per chunk
+  ops.check_face_indices('bake_texture', m['faces'], m['vertices'].shape[0])   # once, not per chunk
   H, W, total = layout['H'], layout['W'], layout['n_samples']
   texture = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
   mask = torch.zeros((H, W), dtype=torch.uint8, device=dev)
@@ -501,7 +504,7 @@ def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=Non
   if k > 1:
     P[:2] *= np.float32(k)
   h, w = k * height, k * width
-  dm = dict(vertices=m['vertices'].contiguous(), normals=m['normals'].contiguous(), faces=m['faces'].contiguous())
+  dm = _device_mesh(m)
   dev = dm['vertices'].device
   if colors is True:
     colors = m.get('colors')

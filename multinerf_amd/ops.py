@@ -1557,6 +1557,60 @@ def image_ingest(src, n_downsample=1, mode='plain', c_out=None, want_alpha=False
   return out, alpha.reshape(shape[1:3] if single else shape[:3])
 
 
+# ----------------------------------------------------------------------------- argument checks the mesh wrappers share
+
+
+def positive_f32(name, label, x):
+  """x as the float32 a kernel sees; ValueError unless that is positive and finite."""
+  x = C.c_float(float(x)).value
+  if not (x > 0. and math.isfinite(x)):
+    raise ValueError(f'{name}: {label} = {x} must be positive and finite in float32')
+  return x
+
+
+def finite3(name, label, v):
+  """v (3 numbers or a tensor of 3) as a list of floats; ValueError unless there are three and all are finite."""
+  v = [float(x) for x in (v.tolist() if torch.is_tensor(v) else v)]
+  if len(v) != 3 or not all(math.isfinite(x) for x in v):
+    raise ValueError(f'{name}: {label} must hold 3 finite values, is {v}')
+  return v
+
+
+def _mesh_tensors(name, verts, faces, normals=None, *, max_faces=2 ** 31 - 1, check_index=False):
+  """(V, T) of an indexed triangle mesh on the device: `verts` [V,3] float32 (or the vertex count V itself, for an entry that reads
+  only the indices), `normals` of the same shape and `faces` [T,3] int32 where given, all contiguous, V below 2^31 and T at most
+  `max_faces` (2^31 - 2 where a face id is the low word of a 64-bit key).  check_index makes one min / max read-back and refuses an
+  index outside the vertices; without it the kernels skip such a face."""
+  if torch.is_tensor(verts):
+    _chk(verts, f32, f'{name}: vertices')
+    _chk(normals, f32, f'{name}: normals', allow_none=True)
+    if verts.dim() != 2 or verts.shape[1] != 3 or (normals is not None and normals.shape != verts.shape):
+      raise ValueError(f'{name}: vertices (and normals) must be [V,3], are {tuple(verts.shape)}'
+                       + ('' if normals is None else f' and {tuple(normals.shape)}'))
+    V = int(verts.shape[0])
+  else:
+    V = int(verts)
+  T = 0
+  if faces is not None:
+    _chk(faces, torch.int32, f'{name}: faces')
+    if faces.dim() != 2 or faces.shape[1] != 3:
+      raise ValueError(f'{name}: faces must be [T,3], is {tuple(faces.shape)}')
+    T = int(faces.shape[0])
+  if not 0 <= V < 2 ** 31 or T > max_faces:
+    raise ValueError(f'{name}: {V} vertices and {T} faces: must lie in 0 .. 2^31 - 1 and 0 .. {max_faces}')
+  if check_index and T > 0:
+    lo, hi = int(faces.min()), int(faces.max())
+    if lo < 0 or hi >= V:
+      raise ValueError(f'{name}: faces holds indices {lo} .. {hi}, outside the {V} vertices')
+  return V, T
+
+
+def check_face_indices(name, faces, n_verts):
+  """ValueError if faces [T,3] int32 holds an index outside [0, n_verts): one min / max read-back.  For a caller that launches many
+  entries on one mesh and passes them check_faces=False, as mesh.bake_texture does for its chunks."""
+  return _mesh_tensors(name, n_verts, faces, check_index=True)
+
+
 # ----------------------------------------------------------------------------- mesh extraction (csrc/mesh.hip)
 
 
@@ -1586,9 +1640,7 @@ def marching_tetrahedra(field, level, origin, spacing, valid=None, return_edges=
   spacing = float(spacing)
   if not (spacing > 0. and math.isfinite(spacing)):
     raise ValueError(f'marching_tetrahedra: spacing must be positive and finite, is {spacing}')
-  origin = [float(v) for v in (origin.tolist() if torch.is_tensor(origin) else origin)]
-  if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
-    raise ValueError(f'marching_tetrahedra: origin must hold 3 finite values, is {origin}')
+  origin = finite3('marching_tetrahedra', 'origin', origin)
   dev = field.device
   nx, ny, nz = (int(v) for v in field.shape)
   n = nx * ny * nz
@@ -1669,9 +1721,7 @@ def tsdf_integrate(tsdf, weight, color, origin, spacing, trunc, proj, depth, acc
   spacing, trunc = float(spacing), float(trunc)
   if not (spacing > 0. and math.isfinite(spacing)) or not (trunc > 0. and math.isfinite(trunc)):
     raise ValueError(f'{name}: spacing and trunc must be positive and finite, are {spacing} and {trunc}')
-  origin = [float(v) for v in (origin.tolist() if torch.is_tensor(origin) else origin)]
-  if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
-    raise ValueError(f'{name}: origin must hold 3 finite values, is {origin}')
+  origin = finite3(name, 'origin', origin)
   a = L.TsdfArgs()
   a.nx, a.ny, a.nz = (int(v) for v in tsdf.shape)
   a.origin[0], a.origin[1], a.origin[2] = origin
@@ -1688,20 +1738,6 @@ def tsdf_integrate(tsdf, weight, color, origin, spacing, trunc, proj, depth, acc
 CC_SWEEPS_PER_READBACK = 4
 
 
-def _chk_faces(name, faces, n_verts):
-  _chk(faces, torch.int32, f'{name}: faces')
-  n_verts = int(n_verts)
-  if faces.dim() != 2 or faces.shape[1] != 3:
-    raise ValueError(f'{name}: faces must be [T,3], is {tuple(faces.shape)}')
-  if not 0 <= n_verts < 2 ** 31 or faces.shape[0] >= 2 ** 31:
-    raise ValueError(f'{name}: {n_verts} vertices and {faces.shape[0]} faces: both must lie in 0 .. 2^31 - 1')
-  if faces.shape[0] > 0:
-    lo, hi = int(faces.min()), int(faces.max())
-    if lo < 0 or hi >= n_verts:
-      raise ValueError(f'{name}: faces holds indices {lo} .. {hi}, outside the {n_verts} vertices')
-  return n_verts, int(faces.shape[0])
-
-
 def mesh_components(faces, n_verts, return_sweeps=False):
   """labels [n_verts] int32 of an indexed triangle mesh (mnr_mesh_cc_init / mnr_mesh_cc_sweep): labels[v] is the smallest vertex
   id v is connected to through face edges, a vertex in no face is its own label.  faces [T,3] int32 on the device; an index
@@ -1709,7 +1745,7 @@ def mesh_components(faces, n_verts, return_sweeps=False):
   sweep of a batch of CC_SWEEPS_PER_READBACK has a device flag of its own, and the batch's flags are read back together (the
   loop's one synchronisation per batch); there is no iteration limit.  Integer min only: two runs agree bit for bit.
   return_sweeps=True appends the number of sweeps up to and including the one that changed nothing."""
-  V, T = _chk_faces('mesh_components', faces, n_verts)
+  V, T = check_face_indices('mesh_components', faces, n_verts)
   labels = torch.empty((V,), dtype=torch.int32, device=faces.device)
   L.check(lib().mnr_mesh_cc_init(V, _ptr(labels), _stream()))
   sweeps = 0
@@ -1726,25 +1762,17 @@ def mesh_components(faces, n_verts, return_sweeps=False):
 
 
 def _chk_cell(name, origin, cell):
-  cell = C.c_float(float(cell)).value                        # what the kernels see
-  if not (cell > 0. and math.isfinite(cell)):
-    raise ValueError(f'{name}: cell must be positive and finite in float32, is {cell}')
-  origin = [float(v) for v in (origin.tolist() if torch.is_tensor(origin) else origin)]
-  if len(origin) != 3 or not all(math.isfinite(v) for v in origin):
-    raise ValueError(f'{name}: origin must hold 3 finite values, is {origin}')
-  return (C.c_float * 3)(*origin), cell
+  return (C.c_float * 3)(*finite3(name, 'origin', origin)), positive_f32(name, 'cell', cell)
 
 
 def mesh_cluster_keys(verts, origin, cell):
   """keys [V] int64 of the vertices' cells (mnr_mesh_cluster_keys; include/mnerf.h): (cx << 42) | (cy << 21) | cz with
   c = int(floor((x - origin) / cell)) in float32, _lib.MESH_KEY_NONFINITE for a vertex that is not finite, _lib.MESH_KEY_OUTSIDE
   for an index outside [0, 2^21).  No read-back: the caller looks at the smallest key."""
-  _chk(verts, f32, 'mesh_cluster_keys: verts')
-  if verts.dim() != 2 or verts.shape[1] != 3:
-    raise ValueError(f'mesh_cluster_keys: verts must be [V,3], is {tuple(verts.shape)}')
+  V, _ = _mesh_tensors('mesh_cluster_keys', verts, None)
   o, cell = _chk_cell('mesh_cluster_keys', origin, cell)
-  keys = torch.empty((verts.shape[0],), dtype=torch.int64, device=verts.device)
-  L.check(lib().mnr_mesh_cluster_keys(_ptr(verts), int(verts.shape[0]), o, cell, _ptr(keys), _stream()))
+  keys = torch.empty((V,), dtype=torch.int64, device=verts.device)
+  L.check(lib().mnr_mesh_cluster_keys(_ptr(verts), V, o, cell, _ptr(keys), _stream()))
   return keys
 
 
@@ -1753,14 +1781,14 @@ def mesh_cluster_faces(faces, vmap, n_clusters):
   `vmap` [V] int32 (mnr_mesh_cluster_faces): the re-indexed face, the same rotated so that its smallest cluster comes first, each
   cluster the face touches once (-1 in the other slots), and whether its three clusters are distinct."""
   name = 'mesh_cluster_faces'
-  _chk(faces, torch.int32, f'{name}: faces')
   _chk(vmap, torch.int32, f'{name}: vmap')
-  if faces.dim() != 2 or faces.shape[1] != 3 or vmap.dim() != 1:
-    raise ValueError(f'{name}: faces must be [T,3] and vmap [V], are {tuple(faces.shape)} and {tuple(vmap.shape)}')
-  T, dev = int(faces.shape[0]), faces.device
+  if vmap.dim() != 1:
+    raise ValueError(f'{name}: vmap must be [V], is {tuple(vmap.shape)}')
+  V, T = _mesh_tensors(name, vmap.shape[0], faces)
+  dev = faces.device
   mapped, canon, incident = (torch.empty((T, 3), dtype=torch.int32, device=dev) for _ in range(3))
   keep = torch.empty((T,), dtype=torch.uint8, device=dev)
-  L.check(lib().mnr_mesh_cluster_faces(_ptr(faces), T, _ptr(vmap), int(vmap.shape[0]), int(n_clusters), _ptr(mapped), _ptr(canon),
+  L.check(lib().mnr_mesh_cluster_faces(_ptr(faces), T, _ptr(vmap), V, int(n_clusters), _ptr(mapped), _ptr(canon),
                                        _ptr(incident), _ptr(keep), _stream()))
   return mapped, canon, incident, keep
 
@@ -1771,15 +1799,14 @@ def mesh_cluster_solve(verts, normals, colors, faces, keys, member_start, member
   cell keys ascending, members [V] int32 with offsets member_start [K+1] int64, cluster_faces [n] int32 with offsets face_start
   [K+1] int64, colors [V,3] uint8 or None.  fallback marks the clusters placed at their centroid."""
   name = 'mesh_cluster_solve'
-  for t, dt, label in ((verts, f32, 'verts'), (normals, f32, 'normals'), (faces, torch.int32, 'faces'), (keys, torch.int64, 'keys'),
-                       (member_start, torch.int64, 'member_start'), (members, torch.int32, 'members'),
+  V, T = _mesh_tensors(name, verts, faces, normals)
+  for t, dt, label in ((keys, torch.int64, 'keys'), (member_start, torch.int64, 'member_start'), (members, torch.int32, 'members'),
                        (face_start, torch.int64, 'face_start'), (cluster_faces, torch.int32, 'cluster_faces')):
     _chk(t, dt, f'{name}: {label}')
   _chk(colors, torch.uint8, f'{name}: colors', allow_none=True)
-  V, T, K = int(verts.shape[0]), int(faces.shape[0]), int(keys.shape[0])
-  if tuple(verts.shape) != (V, 3) or normals.shape != verts.shape or tuple(faces.shape) != (T, 3) or \
-      (colors is not None and colors.shape != verts.shape):
-    raise ValueError(f'{name}: verts, normals and colors must be [V,3] and faces [T,3]')
+  K = int(keys.shape[0])
+  if colors is not None and colors.shape != verts.shape:
+    raise ValueError(f'{name}: colors must be [V,3] like the vertices, is {tuple(colors.shape)}')
   if tuple(member_start.shape) != (K + 1,) or tuple(face_start.shape) != (K + 1,) or tuple(members.shape) != (V,) or cluster_faces.dim() != 1:
     raise ValueError(f'{name}: member_start and face_start must be [K+1], members [V] and cluster_faces a list')
   o, cell = _chk_cell(name, origin, cell)
@@ -1834,17 +1861,7 @@ def _atlas_args(name, m, layout, filter=1.0, check_faces=True):
   (one min / max read-back; check_faces=False is for a caller that has made that check on this mesh, as mesh.bake_texture does
   once for all its chunks: the kernels never read outside the vertices, such a face's samples are invalid)."""
   verts, normals, faces = m['vertices'], m['normals'], m['faces']
-  _chk(verts, f32, f'{name}: vertices')
-  _chk(normals, f32, f'{name}: normals')
-  if verts.dim() != 2 or verts.shape[1] != 3 or normals.shape != verts.shape:
-    raise ValueError(f'{name}: vertices and normals must be [V,3], are {tuple(verts.shape)} and {tuple(normals.shape)}')
-  if check_faces:
-    V, T = _chk_faces(name, faces, verts.shape[0])
-  else:
-    _chk(faces, torch.int32, f'{name}: faces')
-    V, T = int(verts.shape[0]), int(faces.shape[0])
-    if tuple(faces.shape) != (T, 3):
-      raise ValueError(f'{name}: faces must be [T,3], is {tuple(faces.shape)}')
+  V, T = _mesh_tensors(name, verts, faces, normals, check_index=check_faces)
   if layout != atlas_layout(T, layout['cell'], layout['cols']):
     raise ValueError(f'{name}: the layout {layout} is not atlas_layout({T}, {layout["cell"]}, {layout["cols"]})')
   filter = float(filter)
@@ -1917,28 +1934,18 @@ def atlas_uvs(m, layout):
 RASTER_THRESHOLD = 128
 
 
-def _raster_args(name, m, proj, height, width, near):
+def _raster_args(name, m, proj, height, width, near, check_index=False):
   """(RasterArgs with the geometry set, the tensors it points to) of a mesh dict (vertices, normals, faces on the device), a [3,4]
-  projection (host array or tensor; it is passed by value) and the image size."""
+  projection (host array or tensor; it is passed by value) and the image size.  Without check_index the kernels skip a face with an
+  index outside the vertices."""
   verts, normals, faces = m['vertices'], m['normals'], m['faces']
-  _chk(verts, f32, f'{name}: vertices')
-  _chk(normals, f32, f'{name}: normals')
-  if verts.dim() != 2 or verts.shape[1] != 3 or normals.shape != verts.shape:
-    raise ValueError(f'{name}: vertices and normals must be [V,3], are {tuple(verts.shape)} and {tuple(normals.shape)}')
-  _chk(faces, torch.int32, f'{name}: faces')                 # (no index check: the kernels skip a face with an index outside the vertices)
-  if faces.dim() != 2 or faces.shape[1] != 3:
-    raise ValueError(f'{name}: faces must be [T,3], is {tuple(faces.shape)}')
-  V, T = int(verts.shape[0]), int(faces.shape[0])
-  if T >= 2 ** 31 - 1:
-    raise ValueError(f'{name}: {T} faces: must stay below 2^31 - 1 (a face id is the low word of a pixel\'s key)')
+  V, T = _mesh_tensors(name, verts, faces, normals, max_faces=2 ** 31 - 2, check_index=check_index)
   P = [float(v) for v in torch.as_tensor(proj).detach().cpu().reshape(-1).tolist()]
   if len(P) != 12 or not all(math.isfinite(v) for v in P):
     raise ValueError(f'{name}: proj must be a finite [3,4] matrix')
-  height, width, near = int(height), int(width), C.c_float(float(near)).value
+  height, width, near = int(height), int(width), positive_f32(name, 'near', near)
   if height < 1 or width < 1:
     raise ValueError(f'{name}: an image of {height} x {width} pixels: both sides must be at least 1')
-  if not (near > 0. and math.isfinite(near)):
-    raise ValueError(f'{name}: near = {near} must be positive and finite in float32')
   a = L.RasterArgs()
   a.verts, a.normals, a.faces, a.n_verts, a.n_faces = verts.data_ptr(), normals.data_ptr(), faces.data_ptr(), V, T
   a.proj = (C.c_float * 12)(*P)
@@ -1956,9 +1963,7 @@ def raster_visibility(m, proj, height, width, near, cull='none', threshold=None,
   outside the vertices raise ValueError (one min / max read-back; check_faces=False leaves it to the kernels, which skip such
   a face)."""
   name = 'raster_visibility'
-  a, keep = _raster_args(name, m, proj, height, width, near)
-  if check_faces:
-    _chk_faces(name, keep[2], keep[0].shape[0])
+  a, keep = _raster_args(name, m, proj, height, width, near, check_index=check_faces)
   if cull not in L.RASTER_CULL:
     raise ValueError(f"{name}: cull = {cull!r} must be 'none' or 'back'")
   threshold = RASTER_THRESHOLD if threshold is None else int(threshold)
@@ -2007,10 +2012,7 @@ def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1.,
     raise ValueError(f'{name}: uv is given without a texture')
   if colors is not None:
     a.colors, a.colors_u8 = colors.data_ptr(), int(colors.dtype == torch.uint8)
-  bg = [float(v) for v in bg]
-  if len(bg) != 3 or not all(math.isfinite(v) for v in bg):
-    raise ValueError(f'{name}: bg must hold 3 finite values, is {bg}')
-  a.bg = (C.c_float * 3)(*bg)
+  a.bg = (C.c_float * 3)(*finite3(name, 'bg', bg))
   dev = vis.device
   out = dict(face=torch.empty((H, W), dtype=torch.int32, device=dev), depth=torch.empty((H, W), dtype=f32, device=dev),
              acc=torch.empty((H, W), dtype=f32, device=dev), bary=torch.empty((H, W, 3), dtype=f32, device=dev),
@@ -2026,15 +2028,8 @@ def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1.,
 MESH_GRID_PAIRS_PER_FACE = 8
 
 
-def _chk_mesh(name, verts, faces):
-  _chk(verts, f32, f'{name}: verts')
-  _chk(faces, torch.int32, f'{name}: faces')
-  if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
-    raise ValueError(f'{name}: verts must be [V,3] and faces [T,3], are {tuple(verts.shape)} and {tuple(faces.shape)}')
-  V, T = int(verts.shape[0]), int(faces.shape[0])
-  if V >= 2 ** 31 or T >= 2 ** 31 - 1:
-    raise ValueError(f'{name}: {V} vertices and {T} faces: must stay below 2^31 and 2^31 - 1 (a face id is the low word of a key)')
-  return V, T
+def _chk_mesh(name, verts, faces, check_index=False):
+  return _mesh_tensors(name, verts, faces, max_faces=2 ** 31 - 2, check_index=check_index)
 
 
 def mesh_face_areas(verts, faces):
@@ -2104,9 +2099,7 @@ def mesh_grid_build(verts, faces, cell=None):
   V, T = _chk_mesh(name, verts, faces)
   dev = verts.device
   if cell is not None:
-    cell = C.c_float(float(cell)).value
-    if not (cell > 0. and math.isfinite(cell)):
-      raise ValueError(f'{name}: cell must be positive and finite in float32, is {cell}')
+    cell = positive_f32(name, 'cell', cell)
   empty = dict(origin=[0., 0., 0.], hi=[0., 0., 0.], cell=1. if cell is None else cell, dims=[1, 1, 1], n_valid=0, pairs=0,
                cell_start=torch.zeros((2,), dtype=torch.int64, device=dev), pair_faces=torch.zeros((0,), dtype=torch.int32, device=dev))
   if T == 0 or V == 0:
@@ -2170,14 +2163,8 @@ def point_mesh_distance(points, verts, faces, max_dist=None, grid=None, cell=Non
   _chk(points, f32, f'{name}: points')
   if points.dim() != 2 or points.shape[1] != 3:
     raise ValueError(f'{name}: points must be [N,3], is {tuple(points.shape)}')
-  V, T = _chk_mesh(name, verts, faces)
-  if check_faces:
-    _chk_faces(name, faces, V)
-  lim = float('inf')
-  if max_dist is not None:
-    lim = C.c_float(float(max_dist)).value
-    if not (lim > 0. and math.isfinite(lim)):
-      raise ValueError(f'{name}: max_dist = {max_dist} must be positive and finite in float32')
+  V, T = _chk_mesh(name, verts, faces, check_index=check_faces)
+  lim = float('inf') if max_dist is None else positive_f32(name, 'max_dist', max_dist)
   if grid is not None and cell is not None:
     raise ValueError(f'{name}: grid and cell are both given')
   N, dev = int(points.shape[0]), points.device

@@ -13,16 +13,21 @@ _sim = None
 _sim_f32 = None
 
 
+def tool_module(rel):
+  """tools/<rel> executed as a module (the tools are scripts, not a package)."""
+  spec = importlib.util.spec_from_file_location(os.path.basename(rel)[:-3] + '_tool', os.path.join(ROOT, 'tools', rel))
+  mod = importlib.util.module_from_spec(spec)
+  spec.loader.exec_module(mod)
+  return mod
+
+
 def load_sim(f32=False):
   """Build (if stale) and load libmnerf_sim.so (f32: libmnerf_sim_f32.so, the fp32-Dense debug build); binds every prototype of
   multinerf_amd._lib it exports."""
   global _sim, _sim_f32
   if (_sim_f32 if f32 else _sim) is not None:
     return _sim_f32 if f32 else _sim
-  spec = importlib.util.spec_from_file_location('hipsim_build', os.path.join(ROOT, 'tools', 'hipsim', 'build.py'))
-  mod = importlib.util.module_from_spec(spec)
-  spec.loader.exec_module(mod)
-  lib = C.CDLL(mod.build(verbose=False, f32=f32))
+  lib = C.CDLL(tool_module('hipsim/build.py').build(verbose=False, f32=f32))
   lib.mnr_last_error.restype = C.c_char_p
   lib.hipsim_error.restype = C.c_char_p
   lib.hipsim_reset.argtypes = [C.c_int, C.c_long]

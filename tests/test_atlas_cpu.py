@@ -9,6 +9,7 @@ import pytest
 
 from multinerf_amd import _lib, build, mesh, ops
 from tests import atlas_ref as A
+from tests.sim_helpers import tool_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ('mnr_atlas_samples', 'mnr_atlas_store', 'mnr_atlas_uvs')
@@ -130,8 +131,8 @@ def test_entries_lists_and_documents():
   assert f'#define MNR_ATLAS_MIN_CELL {_lib.ATLAS_MIN_CELL}\n' in header and _lib.ATLAS_MIN_CELL == 3 == A.MIN_CELL
   assert 'seam-safe' in header and 'is exactly 0' in header and 'GUTTER' in header
   assert 'atlas.hip' in build.SOURCES and 'atlas.hip' in build.SOURCES_F32
-  for rel in ('tools/hipsim/build.py', 'tools/isa_report.py'):
-    assert "'atlas.hip'" in read(rel), rel
+  for rel, attr in (('hipsim/build.py', 'SOURCES'), ('isa_report.py', 'KERNEL_FILES')):
+    assert 'atlas.hip' in getattr(tool_module(rel), attr), rel
   code = read('multinerf_amd/csrc/atlas.hip').split('#include')[1]
   assert '#pragma clang fp contract(off)' in code and 'atomic' not in code and 'asm' not in code
   assert code.count('atlas_chart_of(') >= 3 and '__host__ __device__' in code      # one helper, the sample and the UV kernel use it

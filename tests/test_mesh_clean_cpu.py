@@ -10,6 +10,7 @@ import pytest
 
 from multinerf_amd import _lib, build
 from tests import mesh_clean_ref as M
+from tests.sim_helpers import tool_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -170,8 +171,8 @@ def test_entries_lists_and_documents():
   assert f'#define MNR_MESH_KEY_NONFINITE ({_lib.MESH_KEY_NONFINITE})' in header and f'#define MNR_MESH_KEY_OUTSIDE ({_lib.MESH_KEY_OUTSIDE})' in header
   assert 'meshclean.hip' in build.SOURCES and 'meshclean.hip' in build.SOURCES_F32
   read = lambda rel: open(os.path.join(ROOT, rel)).read()
-  for rel in ('tools/hipsim/build.py', 'tools/isa_report.py'):
-    assert "'meshclean.hip'" in read(rel), rel
+  for rel, attr in (('hipsim/build.py', 'SOURCES'), ('isa_report.py', 'KERNEL_FILES')):
+    assert 'meshclean.hip' in getattr(tool_module(rel), attr), rel
   code = read('multinerf_amd/csrc/meshclean.hip').split('#include')[1]
   assert '#pragma clang fp contract(off)' in code and 'atomicAdd' not in code and 'asm' not in code and 'float' in code
   cc = code[:code.index('// ---- vertex clustering: keys')]

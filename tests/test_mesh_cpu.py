@@ -11,6 +11,7 @@ import torch
 
 from multinerf_amd import _lib, build, mesh, ops
 from tests import mesh_ref as R
+from tests.sim_helpers import tool_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -237,9 +238,8 @@ def test_entries_lists_and_documents():
   for e in ('mnr_mt_workgroups', 'mnr_mt_classify', 'mnr_mt_emit_vertices', 'mnr_mt_emit_faces'):
     assert e in names and e in _lib._PROTOS and e not in _lib.F32_ABSENT
   assert 'mesh.hip' in build.SOURCES and 'mesh.hip' in build.SOURCES_F32
-  for rel in ('tools/hipsim/build.py', 'tools/isa_report.py'):
-    with open(os.path.join(ROOT, rel)) as f:
-      assert "'mesh.hip'" in f.read(), rel
+  for rel, attr in (('hipsim/build.py', 'SOURCES'), ('isa_report.py', 'KERNEL_FILES')):
+    assert 'mesh.hip' in getattr(tool_module(rel), attr), rel
   with open(os.path.join(build.CSRC, 'mesh.hip')) as f:
     src = f.read()
   assert '#pragma clang fp contract(off)' in src and 'atomic' not in src.split('#include')[1]
@@ -282,3 +282,22 @@ def test_grid_shape_over_many_resolutions():
         assert n == 2 or (n - 2) * spacing < e * (1 - 1e-7), (res, lo, hi, shape)            # and with no point to spare
   for res in (256, 300, 512, 1024):
     assert mesh.grid_shape((-1, -1, -1), (1, 1, 1), res)[0] == (res,) * 3
+
+
+def test_mesh_helpers_are_shared_not_copied():
+  """csrc/mesh_math.h is the one finite test, normalisation, dot / cross / sub and face-index check of the six mesh files, and
+  switches contraction off itself: a copy compiled with FMAs would leave its file's bit-for-bit promise."""
+  import re
+  read = lambda name: open(os.path.join(build.CSRC, name)).read()
+  header = read('mesh_math.h')
+  assert '#pragma clang fp contract(off)' in header
+  assert header.index('#pragma clang fp contract(off)') < header.index('mesh_finite(float')
+  for helper in ('mesh_finite(float', 'mesh_finite(double', 'mesh_normalise(float*', 'mesh_dot(', 'mesh_sub(', 'mesh_cross(', 'mesh_face_ids('):
+    assert header.count(helper) >= 1, helper
+  for name in ('mesh.hip', 'tsdf.hip', 'meshclean.hip', 'atlas.hip', 'raster.hip', 'meshdist.hip'):
+    src = read(name)
+    assert '#include "mesh_math.h"' in src and '#pragma clang fp contract(off)' in src, name
+    own = re.findall(r'\b(?!mesh_)\w+_(?:finite|normalise)\s*\(', src)
+    assert not own, (name, own)
+    assert not re.search(r'(\w+(?:\[\w+\])*) - \1 == 0\.', src), name       # the finite test, written out
+

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from multinerf_amd import _lib, build, models
+from tests.sim_helpers import tool_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ('mnr_ipe_from_gaussians', 'mnr_ipe_from_gaussians_tangent')
@@ -25,9 +26,8 @@ def test_header_declares_and_protos_bind_both_entries():
 
 def test_source_file_is_on_every_build_list():
   assert 'gaussians.hip' in build.SOURCES and 'gaussians.hip' in build.SOURCES_F32
-  for rel in ('tools/hipsim/build.py', 'tools/isa_report.py'):
-    with open(os.path.join(ROOT, rel)) as f:
-      assert "'gaussians.hip'" in f.read(), rel
+  for rel, attr in (('hipsim/build.py', 'SOURCES'), ('isa_report.py', 'KERNEL_FILES')):
+    assert 'gaussians.hip' in getattr(tool_module(rel), attr), rel
   with open(os.path.join(build.CSRC, 'gaussians.hip')) as f:
     src = f.read()
   assert '#pragma clang fp contract(off)' in src and '#include "ipe_math.h"' in src
@@ -38,8 +38,7 @@ def test_encode_body_is_shared_not_copied():
   decide whether a built library is stale."""
   inc = 'ipe_encode_body.inc'
   assert os.path.join(build.CSRC, inc) in build.HEADERS
-  with open(os.path.join(ROOT, 'tools/hipsim/build.py')) as f:
-    assert "'%s'" % inc in f.read()
+  assert os.path.join(build.CSRC, inc) in tool_module('hipsim/build.py').DEPS
   srcs = {}
   for name in sorted(os.listdir(build.CSRC)):
     with open(os.path.join(build.CSRC, name)) as f:

@@ -13,6 +13,7 @@ import pytest
 from multinerf_amd import _lib as L
 from multinerf_amd import configs, raw_utils
 from tests import raw_ref as ref
+from tests.sim_helpers import tool_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ('mnr_raw_demosaic', 'mnr_raw_postprocess', 'mnr_quantile_f64_workspace', 'mnr_quantile_f64',
@@ -113,9 +114,8 @@ def test_header_bindings_and_both_libraries_agree_on_the_new_symbols():
 
 
 def test_simulator_and_tools_list_the_new_kernel_file():
-  for rel in ('tools/hipsim/build.py', 'tools/isa_report.py'):
-    with open(os.path.join(ROOT, rel)) as f:
-      assert "'raw.hip'" in f.read(), rel
+  for rel, attr in (('hipsim/build.py', 'SOURCES'), ('isa_report.py', 'KERNEL_FILES')):
+    assert 'raw.hip' in getattr(tool_module(rel), attr), rel
   digests = json.load(open(os.path.join(ROOT, 'profiles', 'r6_validated_isa.json')))['kernels']
   for kernel in ('raw_demosaic_quad_kernel', 'raw_demosaic_down_kernel', 'raw_postprocess_kernel', 'quantile_f64_hist_kernel',
                  'quantile_f64_above_kernel', 'quantile_f64_final_kernel', 'affine_sums_kernel', 'affine_apply_kernel'):

@@ -12,6 +12,7 @@ import torch
 from multinerf_amd import _lib, build, camera_utils, mesh
 from oracle import camera_utils as ocam
 from tests import tsdf_ref as T
+from tests.sim_helpers import tool_module
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -150,8 +151,8 @@ def test_entries_lists_and_documents():
     assert f'#define MNR_TSDF_MAX_FRAMES {_lib.TSDF_MAX_FRAMES}\n' in f.read()
   assert 'tsdf.hip' in build.SOURCES and 'tsdf.hip' in build.SOURCES_F32
   read = lambda rel: open(os.path.join(ROOT, rel)).read()
-  for rel in ('tools/hipsim/build.py', 'tools/isa_report.py'):
-    assert "'tsdf.hip'" in read(rel), rel
+  for rel, attr in (('hipsim/build.py', 'SOURCES'), ('isa_report.py', 'KERNEL_FILES')):
+    assert 'tsdf.hip' in getattr(tool_module(rel), attr), rel
   src = read('multinerf_amd/csrc/tsdf.hip')
   code = src.split('#include')[1]
   assert '#pragma clang fp contract(off)' in code and 'atomic' not in code and 'asm' not in code

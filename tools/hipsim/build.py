@@ -4,7 +4,7 @@
 
 Plain clang++ (the one hipcc drives), `-I tools/hipsim` first so that <hip/hip_runtime.h> resolves to the shim; the
 kernel sources are the product's own files.  The result exports the same C ABI as libmnerf_hip.so for the translation
-units listed in SOURCES, taking HOST pointers.  Test infrastructure only (see hip/hip_runtime.h).
+units of multinerf_amd/build.py's SOURCES, taking HOST pointers.  Test infrastructure only (see hip/hip_runtime.h).
 """
 
 import concurrent.futures
@@ -15,14 +15,15 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+  sys.path.insert(0, ROOT)
+from multinerf_amd.build import HEADERS, SOURCES, SOURCES_F32, pool_size  # noqa: E402  (the one list of translation units and headers)
+
 CSRC = os.path.join(ROOT, 'multinerf_amd', 'csrc')
 OUT_DIR = os.path.join(HERE, '_build')
 LIB = os.path.join(OUT_DIR, 'libmnerf_sim.so')
 LIB_F32 = os.path.join(OUT_DIR, 'libmnerf_sim_f32.so')       # the fp32-Dense debug build (multinerf_amd/build.py), simulated
-SOURCES = ['api.hip', 'gemm.hip', 'gemm_blk.hip', 'fused_mlp.hip', 'resample.hip', 'features.hip', 'render.hip', 'losses.hip', 'optim.hip', 'refnerf.hip', 'camera.hip', 'robust.hip', 'metrics.hip', 'vis.hip', 'raw.hip', 'ingest.hip', 'gaussians.hip', 'mesh.hip', 'tsdf.hip', 'meshclean.hip', 'atlas.hip', 'raster.hip', 'meshdist.hip']
-SOURCES_F32 = [s for s in SOURCES if s not in ('gemm_blk.hip', 'fused_mlp.hip')]
-DEPS = [os.path.join(CSRC, 'dense_f32.inc'), os.path.join(HERE, 'hipsim.cpp'), os.path.join(HERE, 'selftest.hip'), os.path.join(HERE, 'hip', 'hip_runtime.h'), os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'gemm_nt_body.inc'), os.path.join(CSRC, 'gemm_tn_body.inc'), os.path.join(CSRC, 'gemm_nt_side.inc'), os.path.join(CSRC, 'ray_losses.h'), os.path.join(CSRC, 'ipe_math.h'), os.path.join(CSRC, 'ipe_encode_body.inc'),
-        os.path.join(ROOT, 'include', 'mnerf.h'), os.path.join(ROOT, 'include', 'mnerf_debug.h')]
+DEPS = HEADERS + [os.path.join(HERE, 'hipsim.cpp'), os.path.join(HERE, 'selftest.hip'), os.path.join(HERE, 'hip', 'hip_runtime.h')]
 FLAGS = ['-std=c++17', '-O0', '-fPIC', '-Wno-psabi', '-I', HERE, '-I', CSRC, '-Wall', '-Wno-unused-function', '-Wno-unused-variable',
          '-Wno-unused-but-set-variable', '-Wno-unknown-pragmas', '-Wno-pass-failed']
 
@@ -61,7 +62,7 @@ def build(force=False, verbose=True, f32=False):
     return obj
 
   paths = [os.path.join(CSRC, s) for s in (SOURCES_F32 if f32 else SOURCES)] + [os.path.join(HERE, 'selftest.hip'), os.path.join(HERE, 'hipsim.cpp')]
-  with concurrent.futures.ThreadPoolExecutor(max_workers=len(paths)) as ex:
+  with concurrent.futures.ThreadPoolExecutor(max_workers=pool_size(len(paths))) as ex:
     objs = list(ex.map(compile_one, paths))
   r = subprocess.run([cxx, '-shared', '-fPIC', '-o', lib] + objs, capture_output=True, text=True)
   if r.returncode != 0:

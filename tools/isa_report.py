@@ -17,6 +17,9 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+  sys.path.insert(0, ROOT)
+from multinerf_amd import build  # noqa: E402
 CSRC = os.path.join(ROOT, 'multinerf_amd', 'csrc')
 
 
@@ -151,15 +154,14 @@ def compile_file(name):
   return text
 
 
-KERNEL_FILES = ('gemm.hip', 'gemm_blk.hip', 'fused_mlp.hip', 'resample.hip', 'features.hip', 'render.hip', 'losses.hip', 'optim.hip', 'refnerf.hip',
-                'camera.hip', 'robust.hip', 'metrics.hip', 'vis.hip', 'raw.hip', 'ingest.hip', 'gaussians.hip', 'mesh.hip', 'tsdf.hip', 'meshclean.hip', 'atlas.hip', 'raster.hip', 'meshdist.hip')
+KERNEL_FILES = tuple(s for s in build.SOURCES if s != 'api.hip')       # (api.hip holds no kernel)
 
 
 def all_digests():
   """{kernel name: normalized_digest} over every csrc file."""
   out = {}
   import concurrent.futures
-  with concurrent.futures.ThreadPoolExecutor(max_workers=len(KERNEL_FILES)) as ex:      # (hipcc runs in child processes)
+  with concurrent.futures.ThreadPoolExecutor(max_workers=build.pool_size(len(KERNEL_FILES))) as ex:      # (hipcc runs in child processes)
     texts = list(ex.map(compile_file, KERNEL_FILES))
   for text in texts:
     out.update({n: normalized_digest(b) for n, b in all_kernel_bodies(text).items()})
