@@ -21,7 +21,18 @@ frame to the ground truth's; --geometry_samples, --geometry_thresholds a,b,..., 
 x0,y0,z0,x1,y1,z1 are geometry_metrics' arguments.  --error_ply FILE writes the mesh with its vertices coloured by their distance to
 the ground truth (turbo, 0 .. the largest threshold).  --geometry_only skips the dataset and the rendering: no config is needed.
 
+The Tanks and Temples protocol.  --gt_crop FILE.json is the benchmark's crop volume (a polygonal prism, `mesh.CropVolume.from_json`):
+samples of both shapes outside it are dropped.  --icp point|plane refines --gt_transform (or the identity) by `mesh.register`
+(csrc/meshreg.hip) before scoring: --icp_max_dist a[,b,c] are the correspondence distances of its stages, coarse to fine (required
+with --icp), --icp_iters the updates a stage, --icp_samples the surface samples, --icp_scale estimates a scale too (point only).  It
+prints fitness and RMSE of every stage and the seconds of the registration, writes the refined matrix to
+mesh_gt_transform_refined.txt (four rows of four numbers) and scores, and colours --error_ply, with it.  --geometry_normals adds the
+normal consistency.  There is no voxel down-sampling, no alignment from camera trajectories and no global registration: the
+transform given must already be close.
+
   python eval_mesh.py --mesh barn.ply --geometry_only --gt_mesh Barn.ply --gt_transform Barn_trans.txt --geometry_thresholds 0.01
+  python eval_mesh.py --mesh barn.ply --geometry_only --gt_mesh Barn.ply --gt_transform Barn_trans.txt --gt_crop Barn.json \
+      --icp point --icp_scale --icp_max_dist 0.15,0.05,0.02 --geometry_thresholds 0.01
 """
 
 import argparse
@@ -55,9 +66,23 @@ def parse_args(argv):
   ap.add_argument('--geometry_bbox', default=None, help='x0,y0,z0,x1,y1,z1 in the ground truth\'s frame: samples outside are dropped')
   ap.add_argument('--geometry_only', action='store_true', help='skip the dataset and the rendering (no config needed)')
   ap.add_argument('--error_ply', default=None, help='write the mesh coloured by its vertices\' distance to the ground truth')
+  ap.add_argument('--gt_crop', default=None, help='a Tanks and Temples crop file (JSON: bounding_polygon, orthogonal_axis, axis_min, axis_max)')
+  ap.add_argument('--icp', choices=('none', 'point', 'plane'), default='none', help='refine the transform by ICP before scoring')
+  ap.add_argument('--icp_max_dist', default=None, help='a[,b,c]: the correspondence distance of every ICP stage, coarse to fine')
+  ap.add_argument('--icp_iters', type=int, default=30, help='updates an ICP stage at the most')
+  ap.add_argument('--icp_scale', action='store_true', help='estimate a scale as well (--icp point only)')
+  ap.add_argument('--icp_samples', type=int, default=200_000, help='surface samples of the mesh that are registered')
+  ap.add_argument('--geometry_normals', action='store_true', help='add the normal consistency')
   args = ap.parse_args(argv)
-  if (args.geometry_only or args.error_ply or args.gt_transform) and not args.gt_mesh:
-    raise SystemExit('eval_mesh.py: --geometry_only, --error_ply and --gt_transform need --gt_mesh')
+  if (args.geometry_only or args.error_ply or args.gt_transform or args.gt_crop or args.icp != 'none' or args.geometry_normals) and not args.gt_mesh:
+    raise SystemExit('eval_mesh.py: --geometry_only, --error_ply, --gt_transform, --gt_crop, --icp and --geometry_normals need --gt_mesh')
+  if args.icp != 'none':
+    try:
+      args.icp_max_dist = [float(v) for v in (args.icp_max_dist or '').split(',')]
+    except ValueError:
+      raise SystemExit('eval_mesh.py: --icp needs --icp_max_dist a[,b,c], positive distances') from None
+    if args.icp == 'plane' and args.icp_scale:
+      raise SystemExit('eval_mesh.py: --icp_scale needs --icp point')
   try:
     args.geometry_thresholds = None if args.geometry_thresholds is None else [float(v) for v in args.geometry_thresholds.split(',')]
     args.geometry_bbox = None if args.geometry_bbox is None else [float(v) for v in args.geometry_bbox.split(',')]
@@ -104,9 +129,25 @@ def score_geometry(args, dm, out_dir):
       raise SystemExit(f'eval_mesh.py: {args.gt_transform} must hold 16 numbers, holds {transform.shape[0]}')
     transform = transform.reshape(4, 4)
   print(f'{args.gt_mesh}: {len(gt["vertices"])} vertices, {len(gt["faces"])} faces' + ('' if len(gt['faces']) else ' (a point cloud)'))
+  crop = mesh.CropVolume.from_json(args.gt_crop) if args.gt_crop else None
+  if args.icp != 'none':
+    torch.cuda.synchronize()
+    t0 = time.time()
+    reg = mesh.register(dm, gt, init=transform, max_dist=args.icp_max_dist, mode=args.icp, with_scale=args.icp_scale,
+                        max_iters=args.icp_iters, n_samples=args.icp_samples, crop=crop)
+    torch.cuda.synchronize()
+    seconds = time.time() - t0
+    for stage, md in enumerate(args.icp_max_dist):
+      h = [e for e in reg['history'] if e['stage'] == stage]
+      print(f'ICP stage {stage} (max_dist {md:g}): {len(h) - 1} iterations, fitness {h[0]["fitness"]:.6f} -> {h[-1]["fitness"]:.6f}, '
+            f'rmse {h[0]["inlier_rmse"]:.6g} -> {h[-1]["inlier_rmse"]:.6g}')
+    print(f'ICP seconds: {seconds:.4f} ({reg["iterations"]} iterations, {args.icp})')
+    transform = reg['transform']
+    np.savetxt(os.path.join(out_dir, 'mesh_gt_transform_refined.txt'), transform, fmt='%.17g')
+  extra = dict(crop=crop, normals=True) if args.geometry_normals else dict(crop=crop) if crop is not None else {}
   timings = {}
   metrics = mesh.geometry_metrics(dm, gt, n_samples=args.geometry_samples, thresholds=args.geometry_thresholds, max_dist=args.geometry_max_dist,
-                                  transform=transform, bbox=args.geometry_bbox, timings=timings)
+                                  transform=transform, bbox=args.geometry_bbox, timings=timings, **extra)
   for name, value in metrics.items():
     print(f'{name} = {value:.9g}')
   with open(os.path.join(out_dir, 'mesh_metric_geometry.txt'), 'w') as f:

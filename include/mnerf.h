@@ -1307,6 +1307,58 @@ int mnr_mesh_face_areas(const float* verts, int64_t n_verts, const int* faces, i
 int mnr_mesh_sample(const float* verts, int64_t n_verts, const int* faces, int64_t n_faces, const double* cum, int64_t n,
                     uint32_t seed, float* points, int* face, void* stream);
 
+/* ------------------------------------------------------------------------- *
+ * Mesh registration: closest points, ICP normal equations, polygonal crop volumes  (csrc/meshreg.hip)
+ * The notation, the validity of a face and the distance formula are those of "Mesh geometry" above; float32 in the order written
+ * unless it says float64, no contraction; tests/registration_ref.py restates everything in NumPy.  No atomics and no reduction
+ * whose order depends on scheduling: two runs agree bit for bit.
+ *
+ * mnr_mesh_closest, one thread a query i of n (n < 2^31): given points [n,3] and face [n] (int32, what mnr_mesh_distance returned;
+ * -1: none) it writes x [n,3], the closest point of the face, and nrm [n,3], the face's unit normal, from the terms of the
+ * distance formula:
+ *   q = (seg(p, a, b), seg(p, b, c), seg(p, c, a));  k = the lowest index of the smallest q (start at 0, replace on <), m = q_k;
+ *   with (u, v) the ends of segment k and t its clamped parameter (seg's own t):  x = u + t (v - u)  (difference, product, sum).
+ *   n = cross(b - a, c - a), nn = dot(n, n).  If nn > 0 and s_0 >= 0 and s_1 >= 0 and s_2 >= 0 (the three signs of the distance formula), with h = dot(n, p - a):
+ *   if (h h) / nn <= m:  x = p - (h / nn) n  (quotient, products, differences).
+ *   nrm = n / sqrt(nn) (sqrt and three quotients) if nn > 0 and finite, else 0.
+ * So x is the foot of the term that gave d2 (the plane term on a tie), and |p - x|^2 is that d2 up to the rounding of forming x.
+ * With vnormals [n_verts,3] (float32, or NULL) a face (i, i, i), a cloud's point, takes nrm = vnormals[i] / |vnormals[i]| (the length
+ * as sqrt(dot), three quotients; 0 if the length is 0 or not finite) in place of the face's.  face[i] outside [0, n_faces), a face
+ * that is not valid, or a point with a coordinate that is not finite: x = p, nrm = 0.
+ *
+ * mnr_mesh_face_normals: nrm [n_faces,3] = n / sqrt(nn) by the same expression; 0 for a face that is not valid, or whose nn is not
+ * positive and finite.
+ *
+ * mnr_icp_sums: over the correspondences i with keep[i] != 0 (uint8 [n], n < 2^31), float64 throughout from the float32 p, x, nrm
+ * [n,3] widened first, with `centre` c (double [3] on the HOST, finite), p' = p - c, x' = x - c, d = p - x, r = dot(d, nrm),
+ * J = (cross(p', nrm), nrm) (6 entries), out [MNR_ICP_SUMS] (float64) receives the sums of
+ *   [0] 1   [1..3] p'   [4..6] x'   [7..15] p'_k x'_l at 7 + 3 k + l   [16] dot(p', p')   [17] dot(x', x')   [18] dot(d, d)   [19] r r
+ *   [20..40] J_k J_l for k <= l, row by row ((0,0), (0,1), .. (0,5), (1,1), ..)   [41..46] J_k r.
+ * Point to point (Kabsch, Umeyama) needs [0..17], point to plane solves (sum J^T J) xi = -(sum J^T r) for xi = (rotation vector about c,
+ * translation); [18] and [19] are the two squared residuals.  The reduction has two levels with nothing left to the scheduler:
+ * B = min(ceil(n / 256), 256) workgroups; thread t of workgroup b adds the terms of i = 256 b + t + 256 B k in ascending k; the 256
+ * threads' sums of an entry are added as 16 sums of the threads s, 16 + s, .., 240 + s (ascending), s = 0 .. 15, and those 16 in
+ * ascending s; `partials`, a workspace of mnr_icp_sums_partials(n) doubles, holds the B results, which are added as four runs of
+ * ceil(B / 4) consecutive workgroups (ascending) and those four in order.  n == 0: out = 0.
+ *
+ * mnr_crop_polygon, one thread a point of n (n < 2^31): keep [n] (uint8) for a polygonal prism, float64 throughout from the float32
+ * points widened first.  With (u, v, w) the coordinate indices for the orthogonal `axis` (0 X: 1, 2, 0;  1 Y: 0, 2, 1;  2 Z: 0, 1, 2) and
+ * polygon [m,2] (float64, on the device) the corners' (u, v), a point is kept iff w_min <= p_w <= w_max and the number of edges
+ * (P_i, P_j), j = i + 1 mod m, with
+ *   (P_i.v > p_v) != (P_j.v > p_v)  and  p_u < ((P_j.u - P_i.u) (p_v - P_i.v)) / (P_j.v - P_i.v) + P_i.u
+ * is odd.  3 <= m <= MNR_CROP_MAX_POLYGON (every thread walks every edge); a point with a NaN coordinate is not kept.
+ * ------------------------------------------------------------------------- */
+#define MNR_ICP_SUMS 47
+#define MNR_CROP_MAX_POLYGON 4096
+int mnr_mesh_closest(const float* verts, int64_t n_verts, const int* faces, int64_t n_faces, const float* vnormals, const float* points,
+                     const int* face, int64_t n, float* x, float* nrm, void* stream);
+int mnr_mesh_face_normals(const float* verts, int64_t n_verts, const int* faces, int64_t n_faces, float* nrm, void* stream);
+int mnr_icp_sums_partials(int64_t n);
+int mnr_icp_sums(int64_t n, const float* p, const float* x, const float* nrm, const uint8_t* keep, const double* centre, double* partials,
+                 double* out, void* stream);
+int mnr_crop_polygon(const float* points, int64_t n, const double* polygon, int m, int axis, double w_min, double w_max, uint8_t* keep,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

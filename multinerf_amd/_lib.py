@@ -251,6 +251,10 @@ class RasterArgs(C.Structure):
 MESHDIST_MAX_DIM = 1024            # MNR_MESHDIST_MAX_DIM
 
 
+ICP_SUMS = 47                      # MNR_ICP_SUMS
+CROP_MAX_POLYGON = 4096            # MNR_CROP_MAX_POLYGON
+
+
 class MeshDistArgs(C.Structure):
   _fields_ = [('verts', vp), ('faces', vp), ('n_verts', C.c_int64), ('n_faces', C.c_int64), ('origin', C.c_float * 3), ('hi', C.c_float * 3),
               ('cell', C.c_float), ('dims', C.c_int * 3)]
@@ -366,6 +370,11 @@ _PROTOS = {
     'mnr_mesh_distance': ([C.POINTER(MeshDistArgs), vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp], i32),
     'mnr_mesh_face_areas': ([vp, i64, vp, i64, vp, vp], i32),
     'mnr_mesh_sample': ([vp, i64, vp, i64, vp, i64, C.c_uint32, vp, vp, vp], i32),
+    'mnr_mesh_closest': ([vp, i64, vp, i64, vp, vp, vp, i64, vp, vp, vp], i32),
+    'mnr_mesh_face_normals': ([vp, i64, vp, i64, vp, vp], i32),
+    'mnr_icp_sums_partials': ([i64], i32),
+    'mnr_icp_sums': ([i64, vp, vp, vp, vp, C.POINTER(C.c_double), vp, vp, vp], i32),
+    'mnr_crop_polygon': ([vp, i64, vp, i32, i32, C.c_double, C.c_double, vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

@@ -14,6 +14,9 @@
   render_mesh    rasterise a mesh from a camera: face ids, depth, barycentrics, normals, colour (csrc/raster.hip)
   sample_surface / point_mesh_distance / geometry_metrics   area-stratified surface samples, the distance of points to a mesh or
                  point cloud, and accuracy, completeness, Chamfer and F-score against a ground truth (csrc/meshdist.hip)
+  closest_points / CropVolume / register   the closest point and normal on a mesh, Tanks and Temples' polygonal crop volumes, and
+                 ICP refinement (point to surface with optional scale, point to plane) of a mesh against its ground truth
+                 (csrc/meshreg.hip); geometry_metrics takes `crop`, `refine` and `normals`
   read_ply_geometry   a tolerant PLY reader for ground-truth meshes and point clouds
 
 Grid convention (the kernels' own): field[i, j, k] sits at origin + spacing * (i, j, k), the linear point index is
@@ -722,11 +725,235 @@ def point_mesh_distance(points, m, max_dist=None, grid=None):
   return dict(distance=torch.sqrt(d2), face=face)
 
 
+def _vnormals(m, verts):
+  """The per-vertex normals of a shape dict as [V,3] float32 on the device of `verts`, or None."""
+  n = m.get('normals') if isinstance(m, dict) else None
+  if n is None:
+    return None
+  n = torch.as_tensor(n).to(device=verts.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+  if n.shape != verts.shape:
+    raise ValueError(f'normals must be [{verts.shape[0]},3] like the vertices, are {tuple(n.shape)}')
+  return n
+
+
+def closest_points(points, m, max_dist=None, grid=None):
+  """dict(point [N,3] float32, normal [N,3] float32, distance [N] float32, face [N] int32): the closest point of the surface of `m`
+  to every point, the unit normal of the face it lies on (for a point cloud with `normals`: the nearest point's normal,
+  normalised; without: 0), and `point_mesh_distance`'s distance and face (ops.mesh_closest; include/mnerf.h: the point is the foot
+  of the very term of the distance formula that gave the distance).  Where no face counts (`max_dist`) or the point is not
+  finite: point = the query itself, normal = 0, distance = +inf, face = -1."""
+  verts, faces = _shape(m)
+  cloud = faces.shape[0] == 0
+  if cloud:
+    faces = _cloud_faces(verts)
+  points = torch.as_tensor(points).to(device=verts.device, dtype=torch.float32).reshape(-1, 3).contiguous()
+  d2, face = ops.point_mesh_distance(points, verts, faces, max_dist=max_dist, grid=grid, check_faces=False)
+  x, nrm = ops.mesh_closest(points, face, verts, faces, vnormals=_vnormals(m, verts) if cloud else None)
+  return dict(point=x, normal=nrm, distance=torch.sqrt(d2), face=face)
+
+
+class CropVolume:
+  """A polygonal prism: the crop volume of the Tanks and Temples evaluation (the JSON files next to its ground truth).  `polygon`
+  is a list of corners, [m,2] in the plane orthogonal to `axis` ('X': (y, z), 'Y': (x, z), 'Z': (x, y)) or [m,3] xyz of which the
+  orthogonal coordinate is ignored; the prism reaches from axis_min to axis_max along the axis, both ends included.  A point is
+  inside iff the even-odd crossing count over the polygon's edges is odd (ops.crop_polygon, csrc/meshreg.hip, float64; the rule is
+  stated in include/mnerf.h).  This is Open3D's SelectionPolygonVolume rule as far as it could be restated from memory: agreement
+  with Open3D itself is UNVERIFIED."""
+
+  AXES = {'X': 0, 'Y': 1, 'Z': 2}
+  _UV = {0: (1, 2), 1: (0, 2), 2: (0, 1)}
+
+  def __init__(self, polygon, axis, axis_min, axis_max):
+    ax = self.AXES.get(str(axis).upper()) if not isinstance(axis, (int, np.integer)) else int(axis)
+    if ax not in (0, 1, 2):
+      raise ValueError(f'CropVolume: axis must be X, Y or Z (or 0, 1, 2), is {axis!r}')
+    poly = np.asarray(_host(polygon, np.float64), dtype=np.float64)
+    if poly.ndim != 2 or poly.shape[1] not in (2, 3):
+      raise ValueError(f'CropVolume: polygon must be [m,2] or [m,3], is {poly.shape}')
+    if poly.shape[1] == 3:
+      poly = poly[:, list(self._UV[ax])]
+    if not 3 <= poly.shape[0] <= L.CROP_MAX_POLYGON:
+      raise ValueError(f'CropVolume: a polygon of {poly.shape[0]} corners: must have 3 .. {L.CROP_MAX_POLYGON}')
+    lo, hi = float(axis_min), float(axis_max)
+    if not (np.isfinite(poly).all() and math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+      raise ValueError('CropVolume: the polygon, axis_min and axis_max must be finite, with axis_min <= axis_max')
+    self.polygon, self.axis, self.axis_min, self.axis_max = np.ascontiguousarray(poly), ax, lo, hi
+
+  @classmethod
+  def from_json(cls, path):
+    """The crop file of the Tanks and Temples toolbox: the keys bounding_polygon (a list of xyz), orthogonal_axis, axis_min and
+    axis_max; any other key is ignored.  One ValueError names every key that is missing."""
+    import json
+    with open(path) as f:
+      d = json.load(f)
+    keys = ('bounding_polygon', 'orthogonal_axis', 'axis_min', 'axis_max')
+    missing = [k for k in keys if not isinstance(d, dict) or k not in d]
+    if missing:
+      raise ValueError(f'CropVolume.from_json: {path} lacks {", ".join(missing)}')
+    return cls(d['bounding_polygon'], d['orthogonal_axis'], d['axis_min'], d['axis_max'])
+
+  def contains(self, points):
+    """bool [N]: which of the points [N,3] (rounded to float32, on the device) lie inside."""
+    pts = torch.as_tensor(points)
+    pts = pts.to(device=pts.device if pts.is_cuda else 'cuda', dtype=torch.float32).reshape(-1, 3).contiguous()
+    poly = torch.from_numpy(self.polygon).to(pts.device)
+    return ops.crop_polygon(pts, poly, self.axis, self.axis_min, self.axis_max) != 0
+
+
+ICP_MODES = ('point', 'plane')
+
+
+def _finite_4x4(name, M):
+  M = np.asarray(_host(M, np.float64), dtype=np.float64).reshape(-1)
+  if M.shape != (16,) or not np.isfinite(M).all():
+    raise ValueError(f'{name} must be a finite 4 x 4 matrix')
+  return M.reshape(4, 4)
+
+
+def _rodrigues(w):
+  th = float(np.linalg.norm(w))
+  K = np.array([[0., -w[2], w[1]], [w[2], 0., -w[0]], [-w[1], w[0], 0.]])
+  if th < 1e-12:
+    return np.eye(3) + K
+  return np.eye(3) + (math.sin(th) / th) * K + ((1. - math.cos(th)) / (th * th)) * (K @ K)
+
+
+def icp_step(sums, centre, mode, with_scale=False):
+  """The 4 x 4 float64 update of one ICP iteration from the 47 sums of ops.icp_sums (host, NumPy): 'point': Kabsch on the centred
+  cross-covariance with the determinant fixed, Umeyama's scale with `with_scale`; 'plane': the 6 x 6 normal equations, the rotation
+  by Rodrigues' formula about `centre`."""
+  S, c = np.asarray(sums, dtype=np.float64), np.asarray(centre, dtype=np.float64)
+  n = S[0]
+  D = np.eye(4)
+  if mode == 'point':
+    mp, mx = S[1:4] / n, S[4:7] / n
+    H = S[7:16].reshape(3, 3) / n - np.outer(mp, mx)           # sum (p - mp)(x - mx)^T / n
+    U, sv, Vt = np.linalg.svd(H)
+    sign = np.array([1., 1., 1. if np.linalg.det(Vt.T @ U.T) >= 0. else -1.])
+    R = Vt.T @ np.diag(sign) @ U.T
+    scale = 1.
+    if with_scale:
+      var = S[16] / n - mp @ mp
+      if not var > 0.:
+        raise ValueError('register: the inliers have no spread: no scale can be estimated')
+      scale = float((sv * sign).sum() / var)
+    D[:3, :3] = scale * R
+    D[:3, 3] = (mx + c) - scale * R @ (mp + c)
+  else:
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = S[20:41]
+    A = A + np.triu(A, 1).T
+    xi = np.linalg.lstsq(A, -S[41:47], rcond=1e-12)[0]
+    R = _rodrigues(xi[:3])
+    D[:3, :3] = R
+    D[:3, 3] = c - R @ c + xi[3:]
+  return D
+
+
+def register(pred, gt, init=None, max_dist=None, mode='plane', with_scale=False, max_iters=30, rel_tol=1e-6, n_samples=200_000, seed=0,
+             crop=None, timings=None):
+  """ICP refinement of the pose of `pred` against `gt` (meshes, or point clouds: dicts without faces):
+  dict(transform [4,4] float64 from pred's frame to gt's, fitness, inlier_rmse, iterations, history).
+
+  `pred` is sampled once (`sample_surface`, n_samples, seed; a cloud is its own sample) and the samples outside `crop` (a CropVolume
+  in gt's frame) after `init` (4 x 4, default the identity) are dropped; gt's grid is built once.  An iteration moves the samples by
+  the current transform in float64 on the device, rounds once to float32, finds the nearest face within `max_dist`
+  (ops.point_mesh_distance), the closest point and its normal (ops.mesh_closest) and the 47 sums over the inliers (ops.icp_sums,
+  about the centre of gt's box), reads those back and solves on the host in float64 (`icp_step`); the update is composed on the left.
+    mode 'point': point to surface.  Kabsch; with_scale adds Umeyama's scale.  Converges linearly along the surface.
+    mode 'plane': point to plane, the 6 x 6 system, quadratic near the solution.  Needs normals: a cloud `gt` must carry `normals`.
+  fitness = inliers / samples, inlier_rmse = sqrt(mean |p - x|^2) over the inliers, both OF the returned transform.  It stops when
+  |fitness - previous| and |inlier_rmse - previous| both fall below rel_tol, or after max_iters updates.  `max_dist` (required) may
+  be a sequence: the stages run in the order given (coarse to fine), each from the last one's transform, max_iters each.  `history`
+  lists dict(stage, max_dist, iteration, fitness, inlier_rmse) of every evaluation; `iterations` counts the updates of all stages.
+  ValueError: 'plane' with with_scale or without target normals, an `init` that is not finite, fewer than 6 inliers in a stage.
+
+  What this is not: there is no voxel down-sampling (the samples are stratified in the area already), no initial alignment from
+  camera trajectories and no global registration: a poor `init` converges to a wrong pose.  `timings`, a dict, receives the seconds
+  of `move`, `query`, `closest_sums` (with the read-back) and `solve`, summed over the iterations."""
+  name = 'register'
+  if mode not in ICP_MODES:
+    raise ValueError(f'{name}: mode must be one of {ICP_MODES}, is {mode!r}')
+  if mode == 'plane' and with_scale:
+    raise ValueError(f"{name}: mode 'plane' estimates no scale: use mode 'point' with with_scale")
+  if max_dist is None:
+    raise ValueError(f'{name}: max_dist is required (a distance, or a sequence of them, coarse to fine)')
+  stages = [float(d) for d in (max_dist if isinstance(max_dist, (list, tuple, np.ndarray)) else [max_dist])]
+  if not stages or not all(d > 0. and math.isfinite(d) for d in stages):
+    raise ValueError(f'{name}: max_dist must be positive and finite, is {max_dist}')
+  max_iters, n_samples = int(max_iters), int(n_samples)
+  if max_iters < 0 or n_samples < 1:
+    raise ValueError(f'{name}: max_iters = {max_iters} must not be negative and n_samples = {n_samples} must be positive')
+  T = np.eye(4) if init is None else _finite_4x4(f'{name}: init', init).copy()
+  if not np.array_equal(T[3], [0., 0., 0., 1.]):
+    raise ValueError(f'{name}: init must be affine (last row 0 0 0 1)')
+  gv, gf = _shape(gt)
+  vnormals = None
+  if gf.shape[0] == 0:
+    vnormals = _vnormals(gt, gv)
+    gf = _cloud_faces(gv)
+    if mode == 'plane' and vnormals is None:
+      raise ValueError(f"{name}: mode 'plane' needs normals: the target is a point cloud without `normals`")
+  dev = gv.device
+  clock = {}
+
+  def timed(key, fn):
+    if timings is None:
+      return fn()
+    torch.cuda.synchronize()
+    t0 = time.time()
+    out = fn()
+    torch.cuda.synchronize()
+    clock[key] = clock.get(key, 0.) + time.time() - t0
+    return out
+
+  src = sample_surface(pred, n_samples, seed)['points'].double()
+
+  def move(M):
+    A, t = torch.from_numpy(M[:3, :3].T.copy()).to(dev), torch.from_numpy(M[:3, 3].copy()).to(dev)
+    return (src @ A + t).float().contiguous()
+
+  if crop is not None:
+    src = src[crop.contains(move(T))].contiguous()
+  N = int(src.shape[0])
+  grid = ops.mesh_grid_build(gv, gf)
+  if N == 0 or grid['n_valid'] == 0:
+    raise ValueError(f'{name}: nothing to register: {N} samples, {grid["n_valid"]} valid target faces')
+  centre = [0.5 * (float(a) + float(b)) for a, b in zip(grid['origin'], grid['hi'])]
+  sums = torch.empty((L.ICP_SUMS,), dtype=torch.float64, device=dev)
+  history, updates = [], 0
+  for stage, md in enumerate(stages):
+    prev = None
+    for it in range(max_iters + 1):
+      q = timed('move', lambda: move(T))
+      d2, face = timed('query', lambda: ops.point_mesh_distance(q, gv, gf, max_dist=md, grid=grid, check_faces=False))
+
+      def closest_sums():
+        x, nrm = ops.mesh_closest(q, face, gv, gf, vnormals=vnormals)
+        return ops.icp_sums(q, x, nrm, (face >= 0).to(torch.uint8), centre, out=sums).cpu().numpy()
+      S = timed('closest_sums', closest_sums)
+      if S[0] < 6:
+        raise ValueError(f'{name}: stage {stage} (max_dist {md:g}): {int(S[0])} of {N} samples have a correspondence: at least 6 are needed')
+      fitness, rmse = float(S[0]) / N, math.sqrt(max(float(S[18]), 0.) / float(S[0]))
+      history.append(dict(stage=stage, max_dist=md, iteration=it, fitness=fitness, inlier_rmse=rmse))
+      if it == max_iters or (prev is not None and abs(fitness - prev[0]) < rel_tol and abs(rmse - prev[1]) < rel_tol):
+        break
+      prev = (fitness, rmse)
+      t0 = time.time()
+      T = icp_step(S, centre, mode, with_scale) @ T
+      clock['solve'] = clock.get('solve', 0.) + time.time() - t0
+      updates += 1
+  if timings is not None:
+    timings.update(clock)
+  return dict(transform=T, fitness=history[-1]['fitness'], inlier_rmse=history[-1]['inlier_rmse'], iterations=updates, history=history)
+
+
 # default thresholds of `geometry_metrics` as fractions of the ground truth's bounding-box diagonal
 GEOMETRY_THRESHOLDS = (0.0025, 0.005, 0.01)
 
 
-def geometry_metrics(pred, gt, n_samples=1_000_000, thresholds=None, max_dist=None, seed=0, transform=None, bbox=None, timings=None):
+def geometry_metrics(pred, gt, n_samples=1_000_000, thresholds=None, max_dist=None, seed=0, transform=None, bbox=None, timings=None,
+                     crop=None, refine=None, normals=False):
   """Geometric error of the mesh `pred` against the ground truth `gt` (a mesh, or a point cloud: a dict without faces) as a dict of
   Python floats.  Both surfaces are sampled (`sample_surface`, n_samples points each, seeds `seed` and `seed + 1`; a cloud is its
   own sample); d_acc is the distance of pred's samples to gt (point to triangle, or point to point for a cloud), d_comp that of
@@ -743,16 +970,34 @@ def geometry_metrics(pred, gt, n_samples=1_000_000, thresholds=None, max_dist=No
   publishes for its scenes (3 to 15 mm on scenes of metres); pass the benchmark's own where there are such.
   `transform` is a 4 x 4 matrix from pred's frame to gt's, applied to pred's vertices in float64 on the host before anything else.
   `bbox` (x0, y0, z0, x1, y1, z1) drops the samples of both shapes outside that axis-aligned box of gt's frame; the distances are
-  still taken to the whole of the other shape.  Tanks and Temples' ORIENTED crop volumes and its ICP refinement are not supported.
-  `timings`, a dict, receives the seconds of `sample`, `grid` and `query` (each bracketed by a device synchronisation)."""
+  still taken to the whole of the other shape.
+  `timings`, a dict, receives the seconds of `sample`, `grid` and `query` (each bracketed by a device synchronisation).
+
+  Tanks and Temples' protocol (all three off by default, and then the dict and every bit in it are what they were without them):
+  `crop`, a `CropVolume` (the benchmark's polygonal prism, `CropVolume.from_json`), drops the samples of both shapes outside it, after
+  `transform`, like `bbox`.  `refine`, a dict of `register`'s arguments (at least max_dist), runs the ICP refinement from
+  `transform` (inside `crop`, unless the dict brings its own) and scores with the refined transform, which is returned under the key
+  `transform` as a [4,4] float64 array, the one entry that is not a float.  `normals=True` adds normal_consistency_acc,
+  normal_consistency_comp and normal_consistency, their mean: the mean over the samples of |m_i . n_i|, m_i the unit normal of the
+  face the sample was drawn from (a cloud's own `normals`, normalised) and n_i that of the closest face of the other shape
+  (`closest_points`); only pairs with both normals non-zero count (NaN if there is none), and the keys are absent when either
+  shape is a cloud without normals.  Not supported: voxel down-sampling, alignment from camera trajectories, global registration
+  (see `register`)."""
   pv, pf = _shape(pred)
   gv, gf = _shape(gt)
   dev = gv.device
+  if crop is not None and not isinstance(crop, CropVolume):
+    raise ValueError('geometry_metrics: crop must be a CropVolume')
+  if refine is not None:
+    kw = dict(refine)
+    kw.setdefault('crop', crop)
+    kw.setdefault('init', transform)
+    transform = register(pred, gt, **kw)['transform']
+  pn, gn = (_vnormals(pred, pv), _vnormals(gt, gv)) if normals else (None, None)
   if transform is not None:
-    M = np.asarray(_host(transform, np.float64)).reshape(-1)
-    if M.shape != (16,) or not np.isfinite(M).all():
-      raise ValueError('geometry_metrics: transform must be a finite 4 x 4 matrix')
-    M = M.reshape(4, 4)
+    M = _finite_4x4('geometry_metrics: transform', transform)
+    if pn is not None and pf.shape[0] == 0:                   # a cloud's normals move with it: n A^-1 (row form of the inverse transpose)
+      pn = torch.from_numpy((_host(pn, np.float64) @ np.linalg.inv(M[:3, :3])).astype(np.float32)).to(dev)
     h = _host(pv, np.float64) @ M[:3, :3].T + M[:3, 3]
     w = _host(pv, np.float64) @ M[3, :3] + M[3, 3]
     pv = torch.from_numpy((h / w[:, None]).astype(np.float32)).to(dev)
@@ -779,23 +1024,38 @@ def geometry_metrics(pred, gt, n_samples=1_000_000, thresholds=None, max_dist=No
 
   shapes = {'pred': (pv, pf if pf.shape[0] else None), 'gt': (gv, gf if gf.shape[0] else None)}
   as_dict = lambda k: dict(vertices=shapes[k][0], faces=shapes[k][1])
-  samples = {k: timed('sample', lambda k=k: sample_surface(as_dict(k), n_samples, seed + (k == 'gt'))['points']) for k in shapes}
+  drawn = {k: timed('sample', lambda k=k: sample_surface(as_dict(k), n_samples, seed + (k == 'gt'))) for k in shapes}
+  samples, drawn_face = {k: d['points'] for k, d in drawn.items()}, {k: d['face'] for k, d in drawn.items()}
   if bbox is not None:
     box = [float(v) for v in bbox]
     if len(box) != 6 or not all(math.isfinite(v) for v in box) or any(box[d] > box[d + 3] for d in range(3)):
       raise ValueError(f'geometry_metrics: bbox must be x0, y0, z0, x1, y1, z1 with x0 <= x1 ..., is {bbox}')
     lo, hi = torch.tensor(box[:3], device=dev), torch.tensor(box[3:], device=dev)
-    samples = {k: p[((p >= lo) & (p <= hi)).all(1)].contiguous() for k, p in samples.items()}
+    inside = {k: ((p >= lo) & (p <= hi)).all(1) for k, p in samples.items()}
+    samples, drawn_face = {k: p[inside[k]].contiguous() for k, p in samples.items()}, {k: f[inside[k]] for k, f in drawn_face.items()}
+  if crop is not None:
+    inside = {k: crop.contains(p) for k, p in samples.items()}
+    samples, drawn_face = {k: p[inside[k]].contiguous() for k, p in samples.items()}, {k: f[inside[k]] for k, f in drawn_face.items()}
   if min(p.shape[0] for p in samples.values()) == 0:
     raise ValueError('geometry_metrics: no sample of a shape is left to score')
-  dist = {}
+  vnorm = {'pred': pn, 'gt': gn}
+  with_normals = normals and all(shapes[k][1] is not None or vnorm[k] is not None for k in shapes)
+  dist, consistency = {}, {}
   for key, src, dst in (('acc', 'pred', 'gt'), ('comp', 'gt', 'pred')):
     v, f = shapes[dst]
-    f = _cloud_faces(v) if f is None else f
+    cloud = f is None
+    f = _cloud_faces(v) if cloud else f
     grid = timed('grid', lambda: ops.mesh_grid_build(v, f))
-    d2, _ = timed('query', lambda: ops.point_mesh_distance(samples[src], v, f, max_dist=max_dist, grid=grid, check_faces=False))
+    d2, face = timed('query', lambda: ops.point_mesh_distance(samples[src], v, f, max_dist=max_dist, grid=grid, check_faces=False))
     d = torch.sqrt(d2).double()
     dist[key] = d.clamp(max=float(max_dist)) if max_dist is not None else d
+    if with_normals:
+      n_i = ops.mesh_closest(samples[src], face, v, f, vnormals=vnorm[dst] if cloud else None)[1].double()
+      sv, sf = shapes[src]
+      own = torch.nn.functional.normalize(vnorm[src].double(), dim=1) if sf is None else ops.mesh_face_normals(sv, sf).double()
+      m_i = own[drawn_face[src].long().clamp(min=0)]
+      counted = (n_i != 0).any(1) & (m_i != 0).any(1) & torch.isfinite(m_i).all(1)
+      consistency[key] = float((m_i * n_i).sum(1).abs()[counted].mean()) if bool(counted.any()) else float('nan')
   if timings is not None:
     timings.update(clock)
   out = dict(accuracy=float(dist['acc'].mean()), completeness=float(dist['comp'].mean()))
@@ -805,6 +1065,11 @@ def geometry_metrics(pred, gt, n_samples=1_000_000, thresholds=None, max_dist=No
     P, R = float((dist['acc'] < t).double().mean()), float((dist['comp'] < t).double().mean())
     out[f'precision@{t:g}'], out[f'recall@{t:g}'], out[f'fscore@{t:g}'] = P, R, (2. * P * R / (P + R) if P + R > 0. else 0.)
   out['n_pred'], out['n_gt'] = float(samples['pred'].shape[0]), float(samples['gt'].shape[0])
+  if with_normals:
+    out['normal_consistency_acc'], out['normal_consistency_comp'] = consistency['acc'], consistency['comp']
+    out['normal_consistency'] = 0.5 * (consistency['acc'] + consistency['comp'])
+  if refine is not None:
+    out['transform'] = np.array(transform, dtype=np.float64)
   return out
 
 

@@ -2193,3 +2193,83 @@ def point_mesh_distance(points, verts, faces, max_dist=None, grid=None, cell=Non
   L.check(lib().mnr_mesh_distance(C.byref(a), _ptr(cell_start), _ptr(pair_faces), P, _ptr(points), _ptr(order), N, lim, _ptr(d2), _ptr(face),
                                   _ptr(shells), _stream()))
   return out
+
+
+# ----------------------------------------------------------------------------- mesh registration (csrc/meshreg.hip)
+
+def _chk_points(name, label, t, n=None):
+  _chk(t, f32, f'{name}: {label}')
+  if t.dim() != 2 or t.shape[1] != 3 or (n is not None and t.shape[0] != n):
+    raise ValueError(f'{name}: {label} must be [{"N" if n is None else n},3], is {tuple(t.shape)}')
+  if t.shape[0] >= 2 ** 31:
+    raise ValueError(f'{name}: {t.shape[0]} points: must stay below 2^31')
+  return int(t.shape[0])
+
+
+def mesh_closest(points, face, verts, faces, vnormals=None):
+  """(x [N,3], nrm [N,3]) float32: the closest point of face[i] (int32 [N], what `point_mesh_distance` returned; -1: none) to
+  points[i] and that face's unit normal (mnr_mesh_closest; include/mnerf.h states every operation: x is the foot of the term of
+  the distance formula that gave d2).  With `vnormals` [V,3] a face (i, i, i), a cloud's point, takes vnormals[i] normalised.
+  Where face is -1 or names no valid face, or the point is not finite: x = the point itself, nrm = 0."""
+  name = 'mesh_closest'
+  N = _chk_points(name, 'points', points)
+  V, T = _chk_mesh(name, verts, faces)
+  _chk(face, torch.int32, f'{name}: face')
+  if tuple(face.shape) != (N,):
+    raise ValueError(f'{name}: face must be [{N}], is {tuple(face.shape)}')
+  if vnormals is not None:
+    _chk_points(name, 'vnormals', vnormals, V)
+  x, nrm = torch.empty_like(points), torch.empty_like(points)
+  L.check(lib().mnr_mesh_closest(_ptr(verts), V, _ptr(faces), T, _ptr(vnormals), _ptr(points), _ptr(face), N, _ptr(x), _ptr(nrm), _stream()))
+  return x, nrm
+
+
+def mesh_face_normals(verts, faces):
+  """nrm [T,3] float32: the unit normals cross(b - a, c - a) / |.| of the faces (mnr_mesh_face_normals; include/mnerf.h), 0 for a
+  face that is not valid or has no area."""
+  V, T = _chk_mesh('mesh_face_normals', verts, faces)
+  nrm = torch.empty((T, 3), dtype=f32, device=verts.device)
+  L.check(lib().mnr_mesh_face_normals(_ptr(verts), V, _ptr(faces), T, _ptr(nrm), _stream()))
+  return nrm
+
+
+def icp_sums(p, x, nrm, keep, centre, out=None):
+  """[ICP_SUMS = 47] float64 on the device: the sums of one ICP iteration over the correspondences with keep[i] != 0 (uint8 [N]), in
+  float64 from p, x, nrm [N,3] float32 with `centre` (3 finite numbers) taken off p and x (mnr_icp_sums; include/mnerf.h fixes the
+  layout: count, sum p', sum x', sum p' x'^T, sum |p'|^2, sum |x'|^2, sum |p - x|^2, sum r^2, the upper triangle of sum J^T J and
+  sum J^T r).  Two fixed levels of reduction: two runs agree bit for bit."""
+  name = 'icp_sums'
+  N = _chk_points(name, 'p', p)
+  _chk_points(name, 'x', x, N)
+  _chk_points(name, 'nrm', nrm, N)
+  _chk(keep, torch.uint8, f'{name}: keep')
+  if tuple(keep.shape) != (N,):
+    raise ValueError(f'{name}: keep must be [{N}], is {tuple(keep.shape)}')
+  _chk(out, f64, f'{name}: out', allow_none=True)
+  if out is None:
+    out = torch.empty((L.ICP_SUMS,), dtype=f64, device=p.device)
+  elif tuple(out.shape) != (L.ICP_SUMS,):
+    raise ValueError(f'{name}: out must be [{L.ICP_SUMS}], is {tuple(out.shape)}')
+  c = (C.c_double * 3)(*finite3(name, 'centre', centre))
+  partials = torch.empty((max(lib().mnr_icp_sums_partials(N), 1),), dtype=f64, device=p.device)
+  L.check(lib().mnr_icp_sums(N, _ptr(p), _ptr(x), _ptr(nrm), _ptr(keep), c, _ptr(partials), _ptr(out), _stream()))
+  return out
+
+
+def crop_polygon(points, polygon, axis, w_min, w_max):
+  """keep [N] uint8: 1 where points[i] (float32 [N,3]) lies inside the prism of `polygon` [m,2] float64 (the corners' coordinates in
+  the plane orthogonal to `axis`, 0 / 1 / 2 for X / Y / Z: (y, z), (x, z), (x, y)) between w_min and w_max along the axis, both ends
+  included (mnr_crop_polygon; include/mnerf.h: even-odd crossing count in float64).  3 <= m <= CROP_MAX_POLYGON = 4096."""
+  name = 'crop_polygon'
+  N = _chk_points(name, 'points', points)
+  _chk(polygon, f64, f'{name}: polygon')
+  if polygon.dim() != 2 or polygon.shape[1] != 2 or not 3 <= polygon.shape[0] <= L.CROP_MAX_POLYGON:
+    raise ValueError(f'{name}: polygon must be [m,2] with 3 <= m <= {L.CROP_MAX_POLYGON}, is {tuple(polygon.shape)}')
+  if axis not in (0, 1, 2):
+    raise ValueError(f'{name}: axis = {axis} must be 0, 1 or 2')
+  w_min, w_max = float(w_min), float(w_max)
+  if not (math.isfinite(w_min) and math.isfinite(w_max) and w_min <= w_max):
+    raise ValueError(f'{name}: needs finite w_min <= w_max, are {w_min} and {w_max}')
+  keep = torch.empty((N,), dtype=torch.uint8, device=points.device)
+  L.check(lib().mnr_crop_polygon(_ptr(points), N, _ptr(polygon), int(polygon.shape[0]), int(axis), w_min, w_max, _ptr(keep), _stream()))
+  return keep
