@@ -3,9 +3,12 @@
 
 The mesh is a PLY that `mesh.write_ply` wrote (extract_mesh.py's output): with per-face texture coordinates it is rendered with the
 PNG its `comment TextureFile` line names (looked up next to the file), otherwise with its vertex colours, otherwise as shaded
-normals.  Every view is rasterised on the device (`mesh.render_mesh`, csrc/raster.hip) and scored by `image.MetricHarness` (PSNR and
-SSIM), honouring Config.eval_quantize_metrics and Config.eval_crop_borders as eval.py does.  No checkpoint is needed.  Perspective
-cameras only: a dataset whose cameras `mesh.world_to_pixel` refuses (lens distortion, NDC rays, fisheye) fails with its message.
+normals.  Where the header also names a `comment TextureSH` file (extract_mesh.py --texture_sh) and it lies next to the mesh, every
+pixel is shaded with the texel's spherical harmonics at its own view direction (`ops.shtex_shade`, csrc/shtex.hip), and the script
+says so; --no_view_dependent scores the plain texture instead.  Every view is rasterised on the device (`mesh.render_mesh`,
+csrc/raster.hip) and scored by `image.MetricHarness` (PSNR and SSIM), honouring Config.eval_quantize_metrics and
+Config.eval_crop_borders as eval.py does.  No checkpoint is needed.  Perspective cameras only: a dataset whose cameras
+`mesh.world_to_pixel` refuses (lens distortion, NDC rays, fisheye) fails with its message.
 
 Under --out_dir (default: <mesh file's directory>/mesh_eval) it writes mesh_color_NNN.png for every view and, in eval.py's format
 (one line, values separated by blanks), mesh_metric_psnr.txt, mesh_metric_ssim.txt and mesh_render_times.txt (seconds a view:
@@ -58,6 +61,8 @@ def parse_args(argv):
   ap.add_argument('--near', type=float, default=None, help='surface nearer than this (zc) is not seen; default: Config.near')
   ap.add_argument('--bg', default='1,1,1', help='r,g,b of the pixels no face covers')
   ap.add_argument('--cull', choices=('none', 'back'), default='none')
+  ap.add_argument('--no_view_dependent', action='store_true',
+                  help='score the plain texture although the mesh names a `comment TextureSH` file (spherical harmonics per texel)')
   ap.add_argument('--gt_mesh', default=None, help='a ground-truth PLY (mesh or point cloud): score the geometry against it')
   ap.add_argument('--gt_transform', default=None, help='a text file of 16 numbers: the 4 x 4 matrix from the mesh\'s frame to the ground truth\'s')
   ap.add_argument('--geometry_samples', type=int, default=1_000_000, help='surface samples a shape')
@@ -113,6 +118,10 @@ def load_mesh(path, device):
     png = os.path.join(os.path.dirname(os.path.abspath(path)), m['texture_file'])
     pixels = np.ascontiguousarray(np.asarray(Image.open(png).convert('RGB'), dtype=np.uint8))
     texture = dict(texture=torch.from_numpy(pixels).to(device), uv=torch.from_numpy(np.ascontiguousarray(m['texcoord'])).to(device))
+    if m.get('texture_sh') is not None:
+      if m['texture_sh'].shape[:2] != pixels.shape[:2]:
+        raise SystemExit(f'eval_mesh.py: {m["texture_sh_file"]} is {m["texture_sh"].shape[:2]} texels, the texture {pixels.shape[:2]}')
+      texture['sh'] = torch.from_numpy(m['texture_sh']).to(device)      # float32: read_ply has converted it
   elif m.get('colors') is not None:
     colors = torch.from_numpy(np.ascontiguousarray(m['colors'])).to(device)
   return dm, texture, colors
@@ -185,6 +194,10 @@ def main(argv=None):
   dm, texture, colors = load_mesh(args.mesh, dev)
   source = 'texture' if texture is not None else 'vertex colours' if colors is not None else 'shaded normals'
   print(f'{args.mesh}: {dm["vertices"].shape[0]} vertices, {dm["faces"].shape[0]} faces, colour from {source}')
+  if texture is not None and texture.get('sh') is not None:
+    degree = {1: 0, 4: 1, 9: 2}[int(texture['sh'].shape[2])]
+    print(f'view-dependent texture: spherical harmonics of degree {degree}, ' +
+          ('ignored (--no_view_dependent): the plain texture is scored' if args.no_view_dependent else "shaded at every pixel's view direction"))
   dataset = datasets.load_dataset(args.split, config.data_dir, config, device=dev)
   camtype = 'pano' if getattr(dataset, '_render_spherical', False) else dataset.camtype
   pixtocams = mesh._host(dataset.pixtocams, np.float64)
@@ -201,7 +214,7 @@ def main(argv=None):
     torch.cuda.synchronize()
     t0 = time.time()
     r = mesh.render_mesh(dm, None, None, dataset.height, dataset.width, texture=texture, colors=colors, near=near, bg=args.bg, cull=args.cull,
-                         supersample=args.supersample, proj=proj)
+                         supersample=args.supersample, proj=proj, view_dependent=not args.no_view_dependent)
     torch.cuda.synchronize()
     seconds.append(time.time() - t0)
     gt = torch.as_tensor(dataset.images[idx]).to(device=dev, dtype=torch.float32)[..., :3].contiguous()

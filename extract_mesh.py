@@ -25,6 +25,12 @@ carries per-face texture coordinates next to <out>.png; --out x.obj writes OBJ +
 With --method tsdf the texture comes from the MLP as well; the vertex colours stay the fused ones.  An atlas with a side above
 --texture_max_side is refused before anything is baked.
 
+--texture_sh L (0, 1 or 2; needs --texture) additionally fits, per texel, spherical harmonics of degree L to the MLP's colour over
+the view directions the texel can be seen from (--texture_sh_dirs 2: 42 directions, 3: 92; --texture_sh_lambda: the ridge;
+`mesh.bake_texture(sh_degree=)`, csrc/shtex.hip) and writes them as <out>_sh.npy (--texture_sh_dtype float16 or float32), named in
+the PLY header; eval_mesh.py and mesh.render_mesh then shade every pixel at its own view direction.  A model whose MLP reads no
+view direction is refused: nothing would change.
+
   python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
       --resolution 512 --density_threshold 10 --out garden.ply
   python extract_mesh.py --gin_configs configs/360.gin --gin_bindings "Config.checkpoint_dir = '...'" \
@@ -70,6 +76,11 @@ def parse_args(argv):
   ap.add_argument('--texture_filter', type=float, default=1.0, help="width of a texel's query Gaussian in texels (0: point samples)")
   ap.add_argument('--texture_max_side', type=int, default=16384,
                   help='refuse an atlas with a longer side (a decision: 16384 is the common hardware texture limit)')
+  ap.add_argument('--texture_sh', type=int, default=None, choices=tuple(range(_lib.SHTEX_MAX_DEGREE + 1)),
+                  help='also fit per-texel spherical harmonics of this degree over the view directions (default: off; needs --texture)')
+  ap.add_argument('--texture_sh_dirs', type=int, default=2, choices=(2, 3), help='icosahedron tesselation of the fitted directions: 42 or 92')
+  ap.add_argument('--texture_sh_lambda', type=float, default=1e-3, help='ridge of the fit on all coefficients but the constant (a decision)')
+  ap.add_argument('--texture_sh_dtype', choices=mesh.SH_DTYPES, default='float16', help='storage of <out>_sh.npy')
   # `--bbox -1,-1,-1,1,1,1`: argparse takes a value that starts with '-' and is no plain number for an option; hand it over as --bbox=...
   argv = list(argv)
   for i in range(len(argv) - 1):
@@ -89,6 +100,10 @@ def parse_args(argv):
     raise SystemExit(f'extract_mesh.py: --texture must be 0 (off) or at least {_lib.ATLAS_MIN_CELL}')
   if not (0. <= args.texture_filter < float('inf')) or args.texture_max_side < 1:
     raise SystemExit('extract_mesh.py: --texture_filter must be finite and not negative, --texture_max_side positive')
+  if args.texture_sh is not None and args.texture == 0:
+    raise SystemExit('extract_mesh.py: --texture_sh needs --texture: the harmonics live in the texture atlas')
+  if not (0. <= args.texture_sh_lambda < float('inf')):
+    raise SystemExit('extract_mesh.py: --texture_sh_lambda must be finite and not negative')
   return args, box
 
 
@@ -121,9 +136,9 @@ def clean_up(args, result, spacing, timed):
 
 def bake_and_write(args, model, result, out, timed):
   """Write `result` to `out` (OBJ for an .obj name, else PLY), with a texture atlas baked from the model's NeRF MLP when --texture is
-  set; returns (seconds of the bake, seconds of the file write).  An atlas beyond --texture_max_side stops the script before the
-  bake and names the --simplify factor that would fit."""
-  texture, t_bake = None, 0.
+  set; returns (seconds of the bake, seconds of the file write, of the bake's seconds those of the SH fit).  An atlas beyond
+  --texture_max_side stops the script before the bake and names the --simplify factor that would fit."""
+  texture, t_bake, seconds = None, 0., {}
   n_faces = int(result['faces'].shape[0])
   if args.texture > 0 and n_faces > 0:
     layout = ops.atlas_layout(n_faces, args.texture)
@@ -134,20 +149,26 @@ def bake_and_write(args, model, result, out, timed):
       raise SystemExit(f'extract_mesh.py: the atlas of {n_faces} faces at --texture {args.texture} is {layout["W"]} x {layout["H"]} texels, beyond '
                        f'--texture_max_side {args.texture_max_side}; about --simplify {factor:.1f} would fit')
     print(f'texture: {layout["W"]} x {layout["H"]}, {layout["n_samples"]} samples, cell {args.texture}')
-    texture, t_bake = timed(lambda: mesh.bake_texture(result, model=model, cell=args.texture, filter=args.texture_filter, chunk=args.chunk))
+    sh = {} if args.texture_sh is None else dict(sh_degree=args.texture_sh, sh_dirs=args.texture_sh_dirs, sh_lambda=args.texture_sh_lambda,
+                                                 timings=seconds)
+    texture, t_bake = timed(lambda: mesh.bake_texture(result, model=model, cell=args.texture, filter=args.texture_filter, chunk=args.chunk, **sh))
+    if args.texture_sh is not None:
+      print(f'texture sh: degree {args.texture_sh}, {int(texture["sh_dirs"].shape[0])} directions, {texture["sh_queries"]} colour queries')
   elif args.texture > 0:
     print('texture: the mesh has no faces, nothing to bake')
   os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
   if out.lower().endswith('.obj'):
     if texture is None:
       raise SystemExit('extract_mesh.py: --out x.obj needs --texture (and a mesh with faces): the OBJ writer writes textured meshes')
-    _, t_write = timed(lambda: mesh.write_obj(out, result, texture))
+    _, t_write = timed(lambda: mesh.write_obj(out, result, texture, sh_dtype=args.texture_sh_dtype))
   else:
-    _, t_write = timed(lambda: mesh.write_ply(out, result, texture=texture))
-  return t_bake, t_write
+    _, t_write = timed(lambda: mesh.write_ply(out, result, texture=texture, sh_dtype=args.texture_sh_dtype))
+  return t_bake, t_write, seconds.get('sh', 0.)
 
 
-def _texture_seconds(args, t_bake):
+def _texture_seconds(args, t_bake, t_sh=0.):
+  if args.texture_sh is not None:
+    return f', texture bake {t_bake:.3f} (sh {t_sh:.3f})'
   return f', texture bake {t_bake:.3f}' if args.texture > 0 else ''
 
 
@@ -158,6 +179,8 @@ def main():
   config = configs.load_preset(args.preset, args.gin_bindings) if args.preset else \
       configs.load_config(args.gin_configs, args.gin_bindings, save_config=False)
   model, state, _, _, _ = train_utils.setup_model(config, 20200823, dataset=None, device=dev)
+  if args.texture_sh is not None and not model.nerf_plan.use_viewdirs:
+    raise SystemExit("extract_mesh.py: --texture_sh: this model's MLP reads no view direction, nothing would change")
   if not config.checkpoint_dir or checkpoints.latest_checkpoint(config.checkpoint_dir) is None:
     raise SystemExit(f'extract_mesh.py: no checkpoint in Config.checkpoint_dir = {config.checkpoint_dir!r}')
   state = checkpoints.restore_checkpoint(config.checkpoint_dir, model, state)
@@ -185,11 +208,11 @@ def main():
   result = dict(vertices=verts, normals=normals, faces=faces, colors=colors)
   result, t_comp, t_simp = clean_up(args, result, spacing, timed)
   verts, faces = result['vertices'], result['faces']
-  t_bake, t_write = bake_and_write(args, model, result, out, timed)
+  t_bake, t_write, t_sh = bake_and_write(args, model, result, out, timed)
   stats = mesh.mesh_stats(verts, faces)
   print('mesh_stats: ' + _format_stats(stats))
   print(f'seconds: grid query {t_grid:.3f} ({field.numel() / max(t_grid, 1e-9):.4g} points/s), isosurface {t_iso:.3f}, '
-        f'colour query {t_col:.3f}, file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp) + _texture_seconds(args, t_bake))
+        f'colour query {t_col:.3f}, file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp) + _texture_seconds(args, t_bake, t_sh))
   print(f'wrote {out}')
 
 
@@ -205,7 +228,7 @@ def main_tsdf(args, box, config, model, state, out, timed):
         f'{dataset.height} x {dataset.width} ({args.tsdf_split} split, {args.tsdf_depth})')
   kept_faces = int(result['faces'].shape[0])
   result, t_comp, t_simp = clean_up(args, result, volume.spacing, timed)
-  t_bake, t_write = bake_and_write(args, model, result, out, timed)
+  t_bake, t_write, t_sh = bake_and_write(args, model, result, out, timed)
   stats = mesh.mesh_stats(result['vertices'], result['faces'])
   print('mesh_stats: ' + _format_stats(stats))
   unseen, total = int((volume.weight == 0).sum()), volume.weight.numel()
@@ -213,7 +236,7 @@ def main_tsdf(args, box, config, model, state, out, timed):
   before = int(ops.marching_tetrahedra(volume.field()[0], 0., volume.origin, volume.spacing)[2].shape[0])
   print(f'faces: {before} before the validity filter, {kept_faces} after')
   print(f'seconds: render {seconds["render"]:.3f}, fusion {seconds["fusion"]:.3f}, isosurface {seconds["isosurface"]:.3f}, '
-        f'file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp) + _texture_seconds(args, t_bake))
+        f'file write {t_write:.3f}' + _clean_up_seconds(args, t_comp, t_simp) + _texture_seconds(args, t_bake, t_sh))
   print(f'wrote {out}')
 
 

@@ -1224,6 +1224,74 @@ int mnr_raster_shade(const mnr_raster_args* args, const uint64_t* vis, int* face
                      float* rgb, void* stream);
 
 /* ------------------------------------------------------------------------- *
+ * View-dependent texture: a per-texel spherical-harmonic fit and its shading  (csrc/shtex.hip)
+ * A texel holds K = (L + 1)^2 real SH coefficients per channel, L in 0 .. MNR_SHTEX_MAX_DEGREE, fitted to the colours of D fixed
+ * WORLD directions by weighted ridge least squares over the hemisphere the texel can be seen from, and the shading pass evaluates
+ * them at each pixel's own view direction.  Everything is float32 in the order written unless it says float64, no contraction;
+ * tests/shtex_ref.py restates it in NumPy.  dot, sub and normalise are csrc/mesh_math.h's (the sections above spell them out).  A view
+ * direction points from the eye TO the surface: a direction d sees a surface of unit normal n iff dot(d, n) < 0.
+ *
+ * Basis (index, then the usual name), of a unit direction (x, y, z), without the Condon-Shortley phase:
+ *   0  C0                1  C1 y              2  C1 z              3  C1 x
+ *   4  C2A (x y)         5  C2A (y z)         6  C2B (3 (z z) - 1) 7  C2A (x z)         8  C2C (x x - y y)
+ * with the products in parentheses first.  The constants are the literals below (sqrt(1 / 4 pi), sqrt(3 / 4 pi), sqrt(15 / 4 pi),
+ * sqrt(5 / 16 pi), sqrt(15 / 16 pi)).  There are two evaluations of these formulas: the host table Y [D,K] in float64 (Python, from
+ * the float32 directions converted to float64, the constants as float64), which the fit reads; and a float32 __device__ function
+ * (the constants rounded to float32) in the shading pass.
+ *
+ * Weight.  a = -dot(d_k, n);  w_k = a > 0 ? (a < 1 ? a : 1) : 0, i.e. min(max(a, 0), 1) with NaN and -0 mapped to +0.
+ *   mnr_shtex_weights  one thread per pair: w [n,D] of dirs [D,3] and normals [n,3].
+ *
+ * Fit (mnr_shtex_fit), one thread per texel, float64 from here on; w_k, rgb_kc and lam are converted to float64 exactly.
+ *   A direction is USED iff w_k > 0 and the three values rgb_k. are finite; the rgb of a direction with w_k == 0 is not read.
+ *   Over the used k ascending, for i = 0 .. K - 1:  t = w_k Y_ki;  M_ij += t Y_kj for j = i .. K - 1;  b_ic += t rgb_kc for c = 0, 1, 2;
+ *   and sw += w_k, s_c += w_k rgb_kc.  (All sums start at +0.)
+ *   tr = ((M_00 + M_11) + ...) + M_{K-1,K-1};  mu = (lam tr) / K;  M_ii += mu for i >= 1: the constant term is not regularised.
+ *   Cholesky M = G G^T, rows i = 0 .. K - 1, in a row j = 0 .. i:  s = M_ji;  s -= G_ip G_jp for p = 0 .. j - 1 ascending;
+ *     j < i: G_ij = s / G_jj;   j == i: the PIVOT s must be > 0 and finite, G_ii = sqrt(s).
+ *   Per channel:  forward  s = b_ic;  s -= G_ip y_p for p = 0 .. i - 1 ascending;  y_i = s / G_ii   (i ascending);
+ *                 back     s = y_i;   s -= G_pi x_p for p = i + 1 .. K - 1 ascending;  x_i = s / G_ii   (i descending).
+ *   coef_ic = float32(x_ic), rounded once.
+ *   Fallbacks.  No direction used: every coefficient is 0.  A pivot that is <= 0 or not finite, or a coef that is not finite in
+ *   float32: coef_0c = float32((s_c / sw) / Y_00) (Y_00 the table's first entry; 0 if that is not finite in float32), the other
+ *   coefficients 0: the weighted mean colour as a constant.  Every output is finite.
+ *   No atomics and no reduction across threads: two runs give the same bits.  The 45 + 27 + 4 sums of degree 2 live in float64
+ *   registers; Y is staged in LDS (D K doubles, every lane reads the same address: a broadcast), so D <= MNR_SHTEX_MAX_DIRS.
+ *
+ * Shade (mnr_shtex_shade), one thread per pixel, reads face [H,W] and bary [H,W,3] as mnr_raster_shade wrote them.  For a pixel
+ * with 0 <= face < n_faces whose three indices lie inside the vertices (any other pixel is left untouched and keeps `bg`):
+ *   X = (l_0 v_0 + l_1 v_1) + l_2 v_2;   d = normalise(X - origin), (0, 0, 1) where the length is 0 or not finite;
+ *   (u, v), x, y, fx, fy, xa, xb, ya, yb exactly as in the rasteriser's texture lookup above, on sh [Ht,Wt,K,3] float32;
+ *   per coefficient j and channel c the plane is interpolated in that form:  top = (1 - fx) t[ya,xa] + fx t[ya,xb],  bot likewise
+ *   on row yb,  v_jc = (1 - fy) top + fy bot;
+ *   r_c = Y_0(d) v_0c, then r_c = r_c + Y_j(d) v_jc for j = 1 .. K - 1 ascending;   rgb_c = r_c > 0 ? (r_c < 1 ? r_c : 1) : 0 (NaN: 0).
+ * ------------------------------------------------------------------------- */
+#define MNR_SHTEX_MAX_DEGREE 2
+#define MNR_SHTEX_MAX_DIRS 512
+#define MNR_SH_C0 0.28209479177387814
+#define MNR_SH_C1 0.4886025119029199
+#define MNR_SH_C2A 1.0925484305920792
+#define MNR_SH_C2B 0.31539156525252005
+#define MNR_SH_C2C 0.5462742152960396
+int mnr_shtex_weights(const float* dirs, int64_t n_dirs, const float* normals, int64_t n, float* w, void* stream);
+int mnr_shtex_fit(const float* dirs, const double* Y, int64_t n_dirs, int degree, const float* normals, const float* rgb, int64_t n,
+                  double lam, float* coef, void* stream);
+typedef struct {
+  const float* verts;              /* [n_verts,3] */
+  const int* faces;                /* [n_faces,3] */
+  int64_t n_verts, n_faces;
+  const int* face;                 /* [H,W], mnr_raster_shade's */
+  const float* bary;               /* [H,W,3], mnr_raster_shade's */
+  int H, W;
+  const float* uv;                 /* [n_faces,3,2] */
+  const float* sh;                 /* [Ht,Wt,K,3], K = (degree + 1)^2 */
+  int Ht, Wt;                      /* 1 .. 2^24 each */
+  int degree;                      /* 0 .. MNR_SHTEX_MAX_DEGREE */
+  float origin[3];                 /* the eye, finite */
+} mnr_shtex_shade_args;
+int mnr_shtex_shade(const mnr_shtex_shade_args* args, float* rgb, void* stream);
+
+/* ------------------------------------------------------------------------- *
  * Mesh geometry: point-to-mesh distance over a uniform grid, surface sampling  (csrc/meshdist.hip)
  * Everything is float32 in the order written unless it says float64, no contraction; tests/geometry_ref.py restates it in NumPy,
  * every query against every face.  dot(x, y) = (x_0 y_0 + x_1 y_1) + x_2 y_2;  cross(u, v) = (u_1 v_2 - u_2 v_1, u_2 v_0 - u_0 v_2,

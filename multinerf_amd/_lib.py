@@ -248,6 +248,16 @@ class RasterArgs(C.Structure):
               ('bg', C.c_float * 3)]
 
 
+SHTEX_MAX_DEGREE = 2               # MNR_SHTEX_MAX_DEGREE
+SHTEX_MAX_DIRS = 512               # MNR_SHTEX_MAX_DIRS
+SH_CONSTANTS = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)   # MNR_SH_C0, C1, C2A, C2B, C2C
+
+
+class ShtexShadeArgs(C.Structure):
+  _fields_ = [('verts', vp), ('faces', vp), ('n_verts', C.c_int64), ('n_faces', C.c_int64), ('face', vp), ('bary', vp), ('H', C.c_int),
+              ('W', C.c_int), ('uv', vp), ('sh', vp), ('Ht', C.c_int), ('Wt', C.c_int), ('degree', C.c_int), ('origin', C.c_float * 3)]
+
+
 MESHDIST_MAX_DIM = 1024            # MNR_MESHDIST_MAX_DIM
 
 
@@ -365,6 +375,9 @@ _PROTOS = {
     'mnr_atlas_uvs': ([C.POINTER(AtlasArgs), vp, vp], i32),
     'mnr_raster_visibility': ([C.POINTER(RasterArgs), vp, vp, vp, vp], i32),
     'mnr_raster_shade': ([C.POINTER(RasterArgs), vp, vp, vp, vp, vp, vp, vp, vp], i32),
+    'mnr_shtex_weights': ([vp, i64, vp, i64, vp, vp], i32),
+    'mnr_shtex_fit': ([vp, vp, i64, i32, vp, vp, i64, C.c_double, vp, vp], i32),
+    'mnr_shtex_shade': ([C.POINTER(ShtexShadeArgs), vp, vp], i32),
     'mnr_mesh_grid_count': ([C.POINTER(MeshDistArgs), vp, vp], i32),
     'mnr_mesh_grid_fill': ([C.POINTER(MeshDistArgs), vp, i64, vp, vp, vp], i32),
     'mnr_mesh_distance': ([C.POINTER(MeshDistArgs), vp, vp, i64, vp, vp, i64, f32, vp, vp, vp, vp], i32),

@@ -428,7 +428,48 @@ def _model_color_fn(model):
   return color_fn
 
 
-def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT_CHUNK, cols=None, return_float=False):
+def sh_directions(sh_dirs=2):
+  """dirs [D,3] float32 (a host array) of `bake_texture`'s sh_dirs: an angular tesselation t of the icosahedron
+  (geopoly.generate_basis('icosahedron', t, remove_symmetries=False): 42 directions for 2, 92 for 3), or a caller's [D,3] array,
+  normalised in float64 and rounded to float32."""
+  if isinstance(sh_dirs, (int, np.integer)) and not isinstance(sh_dirs, bool):
+    from multinerf_amd import geopoly
+    d = np.asarray(geopoly.generate_basis('icosahedron', int(sh_dirs), remove_symmetries=False), dtype=np.float64)
+  else:
+    d = _host(sh_dirs, np.float64)
+    if d.ndim != 2 or d.shape[1] != 3:
+      raise ValueError(f'sh_dirs must be a tesselation or a [D,3] array of directions, is an array of shape {d.shape}')
+  if not 1 <= d.shape[0] <= L.SHTEX_MAX_DIRS:
+    raise ValueError(f'sh_dirs: {d.shape[0]} directions: must lie in 1 .. {L.SHTEX_MAX_DIRS}')
+  length = np.sqrt((d * d).sum(-1, keepdims=True))
+  if not (np.isfinite(length).all() and (length > 0.).all()):
+    raise ValueError('sh_dirs: every direction must be finite and not zero')
+  return np.ascontiguousarray((d / length).astype(np.float32))
+
+
+def _bake_sh_chunk(color_fn, layout, start, means, covs, normals, face, dirs, basis, degree, lam, chunk, sh):
+  """The SH part of one `bake_texture` pass over the samples start .. start + n - 1: weights, the colour of every (texel, direction)
+  pair that counts, the fit, and the scatter into sh [H,W,K,3].  Returns the number of colour queries."""
+  n, D = int(means.shape[0]), int(dirs.shape[0])
+  w = ops.shtex_weights(dirs, normals)
+  pairs = torch.nonzero((w > 0) & (face >= 0)[:, None])      # [P,2]: (sample, direction), rows ascending
+  rgb = torch.zeros((n, D, 3), dtype=torch.float32, device=means.device)   # a pair that is not queried is never read by the fit
+  for p0 in range(0, int(pairs.shape[0]), chunk):
+    s, k = pairs[p0:p0 + chunk, 0], pairs[p0:p0 + chunk, 1]
+    got = color_fn(means[s].contiguous(), covs[s].contiguous(), normals[s].contiguous(), dirs[k].contiguous())
+    rgb[s, k] = got.reshape(int(s.shape[0]), 3).to(torch.float32)
+  coef = ops.shtex_fit(dirs, normals, rgb, degree, lam, basis=basis)
+  # the texel of sample s in closed form (include/mnerf.h: s = cell c (c + 1) + Y (c + 1) + X)
+  c, cols = layout['cell'], layout['cols']
+  keep = torch.nonzero(face >= 0)[:, 0]
+  s = keep + start
+  cell, r = s // (c * (c + 1)), s % (c * (c + 1))
+  sh[(cell // cols) * c + r // (c + 1), (cell % cols) * (c + 1) + r % (c + 1)] = coef[keep]
+  return int(pairs.shape[0])
+
+
+def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT_CHUNK, cols=None, return_float=False, sh_degree=None,
+                 sh_dirs=2, sh_lambda=1e-3, timings=None):
   """A texture atlas for the mesh dict `m` (vertices, normals, faces on the device): dict(texture [H,W,3] uint8, mask [H,W] uint8,
   uv [T,3,2] float32, layout[, texture_f32 [H,W,3] float32 with return_float]) of device tensors.
 
@@ -450,8 +491,24 @@ def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT
   forward pass and its backward pass it may run only on the parameters that pass ran on.  Exactly one of color_fn and model is
   given.  A mesh without faces gives a 0 x 0 texture and launches nothing.
 
+  View-dependent texture.  With sh_degree = L in 0 .. 2 the dict gains sh [H,W,K,3] float32, K = (L + 1)^2, sh_degree, sh_dirs
+  [D,3] float32 and sh_queries (the number of colour queries the fit made); texture, mask and uv are baked as before, bit for
+  bit.  Per texel, sh holds the real spherical-harmonic coefficients (csrc/shtex.hip; include/mnerf.h states basis, order and
+  every operation) that fit, channel by channel,
+  color_fn's colour at the D fixed world directions `sh_dirs` (`sh_directions`: an icosahedron tesselation, 2 gives 42 directions
+  and 3 gives 92, or a [D,3] array), in weighted least squares with weight min(max(-d . n, 0), 1): a view direction points from the
+  eye to the surface, so only the hemisphere a texel can be seen from counts, and only those (texel, direction) pairs are queried
+  (half of them on an antipodal set), in sub-chunks of `chunk` pairs; `chunk` bounds the texels of a pass as before.  sh_lambda is
+  a ridge on every coefficient but the constant, relative to the mean diagonal entry of the normal matrix.  Its default 1e-3 is a
+  DECISION, not a derived number: the float64 solve does not need it (on 42 directions the weighted normal matrix of degree 2 has
+  a condition number up to 6.5e3, of degree 1 up to 51), it damps the fit of a noisy MLP colour.  A texel that cannot be solved
+  holds its weighted mean colour as a constant.  `render_mesh` evaluates sh at each pixel's own view direction.  `timings`, a
+  dict, receives the seconds of the SH part under 'sh' (it costs a device synchronisation before and after that part of a pass).
+
   What this is not: charts are uniform per face (a sliver gets as many texels as a fat triangle), there is no chart merging (mip
-  levels below 0 mix neighbouring cells), and the single head-on view direction bakes a specular lobe as seen along -normal."""
+  levels below 0 mix neighbouring cells), and, without sh_degree, the single head-on view direction bakes a specular lobe as seen
+  along -normal.  The SH texture has degree at most 2 (a sharp highlight is blurred), a fixed world direction set, and no occlusion
+  test for a direction: a texel in a crevice is also fitted to directions it is never seen from."""
   if (color_fn is None) == (model is None):
     raise ValueError('bake_texture: exactly one of color_fn and model must be given')
   if model is not None:
@@ -459,6 +516,13 @@ def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT
   chunk = int(chunk)
   if chunk < 1:
     raise ValueError(f'bake_texture: chunk = {chunk} must be positive')
+  if sh_degree is not None:
+    if isinstance(sh_degree, bool) or int(sh_degree) != sh_degree or not 0 <= int(sh_degree) <= L.SHTEX_MAX_DEGREE:
+      raise ValueError(f'bake_texture: sh_degree = {sh_degree!r} must be None or an integer in 0 .. {L.SHTEX_MAX_DEGREE}')
+    sh_degree, sh_lambda = int(sh_degree), float(sh_lambda)
+    if not (sh_lambda >= 0. and math.isfinite(sh_lambda)):
+      raise ValueError(f'bake_texture: sh_lambda = {sh_lambda} must be finite and not negative')
+    dirs_host = sh_directions(sh_dirs)
   m = _device_mesh(m)
   dev = m['vertices'].device
   T = int(m['faces'].shape[0])
@@ -469,19 +533,44 @@ def bake_texture(m, color_fn=None, model=None, cell=8, filter=1.0, chunk=DEFAULT
   mask = torch.zeros((H, W), dtype=torch.uint8, device=dev)
   texture_f32 = torch.zeros((H, W, 3), dtype=torch.float32, device=dev) if return_float else None
   uv = ops.atlas_uvs(m, layout) if T > 0 else torch.zeros((0, 3, 2), dtype=torch.float32, device=dev)
+  if sh_degree is not None:
+    dirs = torch.from_numpy(dirs_host).to(dev)
+    basis = torch.from_numpy(ops.sh_basis(dirs_host, sh_degree)).to(dev)
+    sh = torch.zeros((H, W, (sh_degree + 1) ** 2, 3), dtype=torch.float32, device=dev)
+    queries = 0
   for start in range(0, total, chunk):
     stop = min(start + chunk, total)
     means, covs, normals, viewdirs, face = ops.atlas_samples(m, layout, start, stop, filter=filter, check_faces=False)
     rgb = color_fn(means, covs, normals, viewdirs).reshape(stop - start, 3).to(torch.float32).contiguous()
     ops.atlas_store(m, layout, start, rgb, face, texture, mask, texture_f32, check_faces=False)
+    if sh_degree is not None:
+      if timings is not None:
+        torch.cuda.synchronize()
+        t0 = time.time()
+      queries += _bake_sh_chunk(color_fn, layout, start, means, covs, normals, face, dirs, basis, sh_degree, sh_lambda, chunk, sh)
+      if timings is not None:
+        torch.cuda.synchronize()
+        timings['sh'] = timings.get('sh', 0.) + time.time() - t0
   out = dict(texture=texture, mask=mask, uv=uv, layout=layout)
   if return_float:
     out['texture_f32'] = texture_f32
+  if sh_degree is not None:
+    out.update(sh=sh, sh_degree=sh_degree, sh_dirs=dirs, sh_queries=queries)
   return out
 
 
+def projection_origin(proj):
+  """The eye of a [3,4] projection P = [A | a4] (`world_to_pixel`): the point o with P (o, 1) = 0, o = -A^{-1} a4, 3 float64 values.
+  For world_to_pixel's matrix that is camtoworld[:3, 3].  A singular or non-finite A has no such point: ValueError."""
+  P = _host(proj, np.float64).reshape(3, 4)
+  A, a4 = P[:, :3], P[:, 3]
+  if not np.isfinite(P).all() or np.linalg.matrix_rank(A) < 3:
+    raise ValueError('projection_origin: the left 3 x 3 block of proj is singular or not finite: the projection has no eye')
+  return -np.linalg.solve(A, a4)
+
+
 def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=None, near=0.05, bg=(1., 1., 1.), cull='none', supersample=1,
-                proj=None, threshold=None):
+                proj=None, threshold=None, view_dependent=True, origin=None):
   """The mesh dict `m` (vertices, normals, faces on the device) seen by a perspective camera, rasterised on the device
   (ops.raster_visibility + ops.raster_shade, csrc/raster.hip; include/mnerf.h states the contract): dict(rgb [H,W,3], acc [H,W],
   face [h,w] int32, depth [h,w], bary [h,w,3], normals [h,w,3], proj [3,4] the host matrix that was rendered) of device tensors, float32
@@ -499,11 +588,20 @@ def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=Non
   supersample = k renders at h x w = k height x k width, the first two rows of the matrix scaled by k, and returns rgb and acc
   box-averaged to [height, width] (plain torch); the GEOMETRIC buffers (face, depth, bary, normals) stay at the rendered resolution
   [k height, k width], since averaging ids or depths across a silhouette means nothing.  A mesh without faces gives the background and
-  launches nothing.  `threshold` is ops.raster_visibility's."""
+  launches nothing.  `threshold` is ops.raster_visibility's.
+
+  A texture dict that carries `sh` (bake_texture(..., sh_degree=), or read_ply's texture_sh put there as a [Ht,Wt,K,3] array; float16
+  is converted to float32 once) is VIEW-DEPENDENT: after the shading pass, ops.shtex_shade (csrc/shtex.hip) overwrites rgb, where a
+  face is hit, with the texel's spherical harmonics evaluated at the unit direction from `origin` to the pixel's surface point.
+  origin defaults to the eye: camtoworld[:3, 3], or with proj= `projection_origin(proj)`.  view_dependent=False, or a dict without
+  sh, renders the plain texture exactly as before.  Supersampling follows either."""
   height, width, k = int(height), int(width), int(supersample)
   if height < 1 or width < 1 or k < 1:
     raise ValueError(f'render_mesh: height = {height}, width = {width} and supersample = {k} must be at least 1')
   P = np.array(world_to_pixel(pixtocam, camtoworld) if proj is None else _host(proj, np.float32).reshape(3, 4), dtype=np.float32)
+  use_sh = bool(view_dependent) and texture is not None and texture.get('sh') is not None
+  if use_sh and origin is None:
+    origin = _host(camtoworld, np.float64)[..., :3, 3].reshape(3) if proj is None else projection_origin(proj)
   if k > 1:
     P[:2] *= np.float32(k)
   h, w = k * height, k * width
@@ -522,6 +620,9 @@ def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=Non
   else:
     vis = ops.raster_visibility(dm, P, h, w, near, cull=cull, threshold=threshold)
     out = ops.raster_shade(dm, P, vis, near, bg=bg, **kw)
+    if use_sh:
+      sh = torch.as_tensor(texture['sh']).to(device=dev, dtype=torch.float32).contiguous()
+      ops.shtex_shade(dm, out['face'], out['bary'], kw['uv'], sh, origin, out['rgb'])
   if k > 1:
     out['rgb'] = out['rgb'].reshape(height, k, width, k, 3).mean((1, 3))
     out['acc'] = out['acc'].reshape(height, k, width, k).mean((1, 3))
@@ -560,13 +661,35 @@ def _write_png(path, image):
   Image.fromarray(image, 'RGB').save(path, format='PNG')
 
 
-def write_ply(path, mesh, texture=None):
+SH_DTYPES = ('float16', 'float32')
+
+
+def _sh_array(name, texture, image, sh_dtype):
+  """sh [H,W,K,3] of a texture dict on the host in `sh_dtype`, or None when the dict carries none."""
+  if texture.get('sh') is None:
+    return None
+  if sh_dtype not in SH_DTYPES:
+    raise ValueError(f'{name}: sh_dtype = {sh_dtype!r} must be one of {SH_DTYPES}')
+  sh = _host(texture['sh'], np.float32)
+  if sh.ndim != 4 or sh.shape[:2] != image.shape[:2] or sh.shape[2] not in (1, 4, 9) or sh.shape[3] != 3:
+    raise ValueError(f'{name}: sh must be [{image.shape[0]},{image.shape[1]},K,3] with K = 1, 4 or 9, is {sh.shape}')
+  if sh_dtype == 'float16':
+    sh = np.clip(sh, -65504., 65504.)
+  return sh.astype(np.dtype(sh_dtype))
+
+
+def write_ply(path, mesh, texture=None, sh_dtype='float16'):
   """dict(vertices, normals, faces[, colors]) (device or host arrays) as a PLY file, binary_little_endian 1.0: vertex
   properties x y z nx ny nz (float) and red green blue (uchar) when the mesh has colours; faces as `list uchar int vertex_indices`.
 
   With `texture` (the dict `bake_texture` returns) a face also carries `list uchar float texcoord`, u v of its three corners (the
   layout MeshLab writes and reads), the header names the image in `comment TextureFile <name>.png`, and the image is written as
-  <path without extension>.png next to the file.  Without it the file is byte for byte the one written before textures existed."""
+  <path without extension>.png next to the file.  Without it the file is byte for byte the one written before textures existed.
+
+  A texture with `sh` (bake_texture(..., sh_degree=)) also writes <path without extension>_sh.npy, the array [H,W,K,3], and the
+  header line `comment TextureSH <name>_sh.npy <degree>` after the TextureFile line.  sh_dtype = 'float16' (the default) halves
+  the bytes: a DECISION; each coefficient is rounded to the nearest float16, a relative error of up to 2^-11, and clipped to
+  +-65504; 'float32' writes it as baked.  A texture without sh writes the file it wrote before."""
   verts, normals = _host(mesh['vertices'], np.float32).reshape(-1, 3), _host(mesh['normals'], np.float32).reshape(-1, 3)
   faces, colors = _host(mesh['faces'], np.int32).reshape(-1, 3), _host(mesh.get('colors'), np.uint8)
   if normals.shape != verts.shape or (colors is not None and colors.reshape(-1, 3).shape != verts.shape):
@@ -589,6 +712,10 @@ def write_ply(path, mesh, texture=None):
     f['nt'] = 6
     f['t'] = uv.reshape(-1, 6)
     header += [f'comment TextureFile {os.path.basename(png)}']
+    sh = _sh_array('write_ply', texture, image, sh_dtype)
+    if sh is not None:
+      npy = os.path.splitext(path)[0] + '_sh.npy'
+      header += [f'comment TextureSH {os.path.basename(npy)} {math.isqrt(sh.shape[2]) - 1}']
   header += [f'element vertex {verts.shape[0]}']
   header += [f'property {"uchar" if t == "u1" else "float"} {n}' for n, t in fields]
   header += [f'element face {faces.shape[0]}', 'property list uchar int vertex_indices']
@@ -601,19 +728,23 @@ def write_ply(path, mesh, texture=None):
     fh.write(f.tobytes())
   if texture is not None:
     _write_png(png, image)
+    if sh is not None:
+      np.save(npy, sh)
 
 
 def read_ply(path):
   """A file written by `write_ply` as dict(vertices [V,3] float32, normals [V,3] float32, faces [T,3] int32,
   colors [V,3] uint8 or None) of host arrays; a file with texture coordinates adds texcoord [T,3,2] float32 and texture_file,
-  the name in its `comment TextureFile` line (None without one)."""
+  the name in its `comment TextureFile` line (None without one).  Where the header has a `comment TextureSH <file> <degree>` line
+  and that file lies next to the PLY, texture_sh is its array [H,W,K,3] as float32 (converted once, here) and
+  texture_sh_file its name."""
   with open(path, 'rb') as fh:
     data = fh.read()
   end = data.index(b'end_header\n') + len(b'end_header\n')
   lines = data[:end].decode('ascii').split('\n')
   if lines[0] != 'ply' or lines[1] != 'format binary_little_endian 1.0':
     raise ValueError(f'{path}: not a binary_little_endian 1.0 PLY file')
-  counts, props, element, texture_file = {}, {}, None, None
+  counts, props, element, texture_file, texture_sh = {}, {}, None, None, None
   for line in lines[2:]:
     w = line.split()
     if w[:1] == ['element']:
@@ -623,6 +754,8 @@ def read_ply(path):
       props[element].append(w[1:])
     elif w[:2] == ['comment', 'TextureFile']:
       texture_file = line.split(None, 2)[2]
+    elif w[:2] == ['comment', 'TextureSH'] and len(w) >= 4:
+      texture_sh = (' '.join(w[2:-1]), int(w[-1]))
   fields = [(p[-1], {'float': '<f4', 'uchar': 'u1'}[p[0]]) for p in props.get('vertex', [])]
   if fields[:6] != _VERTEX_FIELDS or fields[6:] not in ([], _COLOR_FIELDS) or props.get('face') not in (_FACE_PROPS, _FACE_UV_PROPS):
     raise ValueError(f'{path}: not the layout write_ply writes')
@@ -637,19 +770,28 @@ def read_ply(path):
              colors=col(('red', 'green', 'blue')) if len(fields) > 6 else None)
   if textured:
     out['texcoord'], out['texture_file'] = np.array(f['t'], dtype=np.float32).reshape(T, 3, 2), texture_file
+    npy = None if texture_sh is None else os.path.join(os.path.dirname(os.path.abspath(path)), texture_sh[0])
+    if npy is not None and os.path.isfile(npy):
+      sh = np.load(npy, allow_pickle=False)
+      if sh.ndim != 4 or sh.shape[2] != (texture_sh[1] + 1) ** 2 or sh.shape[3] != 3 or sh.dtype not in (np.float16, np.float32):
+        raise ValueError(f'{npy}: not the [H,W,{(texture_sh[1] + 1) ** 2},3] float16 or float32 array of a degree-{texture_sh[1]} texture')
+      out['texture_sh'], out['texture_sh_file'] = np.ascontiguousarray(sh, dtype=np.float32), texture_sh[0]
   return out
 
 
-def write_obj(path, mesh, texture):
+def write_obj(path, mesh, texture, sh_dtype='float16'):
   """dict(vertices, normals, faces) with the dict `bake_texture` returns as a Wavefront OBJ: <path> with `v`, `vn` (one a vertex),
   3 T `vt` lines (u v of each face's corners: a vertex has one UV per face it is in) and `f v/vt/vn` lines, 1-based;
   <path without extension>.mtl with one material whose map_Kd is <path without extension>.png, the texture.  Vertex colours are
-  not written: OBJ has no standard place for them."""
+  not written: OBJ has no standard place for them.  A texture with `sh` also writes <path without extension>_sh.npy as `write_ply`
+  does (sh_dtype likewise); OBJ and MTL have no place to name it, so both files are what they are without it and a reader finds
+  the array by its name."""
   verts, normals = _host(mesh['vertices'], np.float32).reshape(-1, 3), _host(mesh['normals'], np.float32).reshape(-1, 3)
   faces = _host(mesh['faces'], np.int32).reshape(-1, 3)
   if normals.shape != verts.shape:
     raise ValueError('write_obj: normals must have one row per vertex')
   image, uv = _texture_arrays('write_obj', texture, faces.shape[0])
+  sh = _sh_array('write_obj', texture, image, sh_dtype)
   base = os.path.splitext(path)[0]
   name = os.path.basename(base)
   num = lambda row: ' '.join(f'{float(x):.9g}' for x in row)
@@ -664,6 +806,8 @@ def write_obj(path, mesh, texture):
   with open(base + '.mtl', 'w') as fh:
     fh.write('\n'.join(['newmtl material0', 'Ka 1 1 1', 'Kd 1 1 1', 'Ks 0 0 0', 'illum 1', f'map_Kd {name}.png']) + '\n')
   _write_png(base + '.png', image)
+  if sh is not None:
+    np.save(base + '_sh.npy', sh)
 
 
 def mesh_stats(verts, faces):

@@ -2022,6 +2022,113 @@ def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1.,
   return out
 
 
+# ----------------------------------------------------------------------------- view-dependent texture (csrc/shtex.hip)
+
+
+def _sh_degree(name, degree):
+  if isinstance(degree, bool) or int(degree) != degree or not 0 <= int(degree) <= L.SHTEX_MAX_DEGREE:
+    raise ValueError(f'{name}: degree = {degree!r} must be an integer in 0 .. {L.SHTEX_MAX_DEGREE}')
+  return int(degree)
+
+
+def sh_basis(dirs, degree):
+  """Y [D,K] float64 (NumPy), K = (degree + 1)^2: the real spherical harmonics of include/mnerf.h at the directions `dirs` [D,3]
+  (a host array or a tensor; they are rounded to float32 first, what the kernels see, and evaluated in float64): the constant, then
+  y, z, x, then xy, yz, 3z^2 - 1, xz, x^2 - y^2, each with its constant.  The directions are taken as they are (unit vectors are
+  the caller's business)."""
+  import numpy as np
+  degree = _sh_degree('sh_basis', degree)
+  d = np.asarray(dirs.detach().cpu().numpy() if torch.is_tensor(dirs) else dirs, dtype=np.float32).astype(np.float64)
+  if d.ndim != 2 or d.shape[1] != 3:
+    raise ValueError(f'sh_basis: dirs must be [D,3], is {d.shape}')
+  x, y, z = d[:, 0], d[:, 1], d[:, 2]
+  c0, c1, c2a, c2b, c2c = L.SH_CONSTANTS
+  cols = [np.full_like(x, c0)]
+  if degree >= 1:
+    cols += [c1 * y, c1 * z, c1 * x]
+  if degree >= 2:
+    cols += [c2a * (x * y), c2a * (y * z), c2b * (3. * (z * z) - 1.), c2a * (x * z), c2c * (x * x - y * y)]
+  return np.ascontiguousarray(np.stack(cols, -1))
+
+
+def _shtex_dirs(name, dirs, normals):
+  _chk(dirs, f32, f'{name}: dirs')
+  _chk(normals, f32, f'{name}: normals')
+  if dirs.dim() != 2 or dirs.shape[1] != 3 or not 1 <= dirs.shape[0] <= L.SHTEX_MAX_DIRS:
+    raise ValueError(f'{name}: dirs must be [D,3] with D in 1 .. {L.SHTEX_MAX_DIRS}, is {tuple(dirs.shape)}')
+  if normals.dim() != 2 or normals.shape[1] != 3 or normals.shape[0] >= 2 ** 31:
+    raise ValueError(f'{name}: normals must be [n,3] with n below 2^31, is {tuple(normals.shape)}')
+  return int(dirs.shape[0]), int(normals.shape[0])
+
+
+def shtex_weights(dirs, normals):
+  """w [n,D] float32: the weight min(max(-dot(d_k, n), 0), 1) of every direction of `dirs` [D,3] for every unit normal of `normals`
+  [n,3] (mnr_shtex_weights; include/mnerf.h).  A view direction points from the eye to the surface, so w > 0 marks the directions
+  a texel can be seen from; NaN gives 0."""
+  D, n = _shtex_dirs('shtex_weights', dirs, normals)
+  w = torch.empty((n, D), dtype=f32, device=normals.device)
+  L.check(lib().mnr_shtex_weights(_ptr(dirs), D, _ptr(normals), n, _ptr(w), _stream()))
+  return w
+
+
+def shtex_fit(dirs, normals, rgb, degree, lam=0., basis=None):
+  """coef [n,K,3] float32, K = (degree + 1)^2: per texel the spherical-harmonic coefficients that fit the colours rgb [n,D,3] float32
+  of the directions `dirs` [D,3] in weighted ridge least squares, weights as in `shtex_weights` for the texel's `normals` [n,3]
+  (mnr_shtex_fit; include/mnerf.h states every operation: float64 normal equations, Cholesky, one rounding to float32).  A direction
+  with weight 0 is not read; one whose colour is not finite is skipped.  `lam` >= 0 is the ridge relative to the mean diagonal
+  entry, on all coefficients but the constant.  A texel whose system cannot be solved gets its weighted mean colour as a constant,
+  one without any usable direction zeros; every output is finite.  `basis` is `sh_basis(dirs, degree)` on the device (float64
+  [D,K]) for a caller that fits many chunks; by default it is computed here."""
+  name = 'shtex_fit'
+  D, n = _shtex_dirs(name, dirs, normals)
+  degree = _sh_degree(name, degree)
+  K = (degree + 1) ** 2
+  lam = float(lam)
+  if not (lam >= 0. and math.isfinite(lam)):
+    raise ValueError(f'{name}: lam = {lam} must be finite and not negative')
+  _chk(rgb, f32, f'{name}: rgb')
+  if tuple(rgb.shape) != (n, D, 3):
+    raise ValueError(f'{name}: rgb must be [{n},{D},3], is {tuple(rgb.shape)}')
+  if basis is None:
+    basis = torch.from_numpy(sh_basis(dirs, degree)).to(normals.device)
+  _chk(basis, torch.float64, f'{name}: basis')
+  if tuple(basis.shape) != (D, K):
+    raise ValueError(f'{name}: basis must be [{D},{K}], is {tuple(basis.shape)}')
+  coef = torch.empty((n, K, 3), dtype=f32, device=normals.device)
+  L.check(lib().mnr_shtex_fit(_ptr(dirs), _ptr(basis), D, degree, _ptr(normals), _ptr(rgb), n, lam, _ptr(coef), _stream()))
+  return coef
+
+
+def shtex_shade(m, face, bary, uv, sh, origin, rgb):
+  """Overwrite rgb [H,W,3] float32, in place, with the view-dependent colour of every pixel that shows a face (mnr_shtex_shade;
+  include/mnerf.h): `face` [H,W] int32 and `bary` [H,W,3] float32 are `raster_shade`'s outputs for the mesh dict `m`, `uv` [T,3,2] and
+  `sh` [Ht,Wt,K,3] float32 (K = 1, 4 or 9 sets the degree) the atlas of mesh.bake_texture(..., sh_degree=), `origin` the eye.  The
+  view direction is the unit vector from the eye to the pixel's surface point; every coefficient plane is looked up bilinearly like
+  a texture, the sum over the basis is clipped to [0, 1].  Pixels with face < 0 keep what rgb holds.  Returns rgb."""
+  name = 'shtex_shade'
+  verts, faces = m['vertices'], m['faces']
+  V, T = _mesh_tensors(name, verts, faces, max_faces=2 ** 31 - 2)
+  _chk(face, torch.int32, f'{name}: face')
+  _chk(bary, f32, f'{name}: bary')
+  _chk(uv, f32, f'{name}: uv')
+  _chk(sh, f32, f'{name}: sh')
+  _chk(rgb, f32, f'{name}: rgb')
+  if face.dim() != 2 or min(face.shape) < 1 or tuple(bary.shape) != tuple(face.shape) + (3,) or tuple(rgb.shape) != tuple(bary.shape):
+    raise ValueError(f'{name}: face must be a non-empty [H,W] and bary and rgb [H,W,3], are {tuple(face.shape)}, {tuple(bary.shape)} and {tuple(rgb.shape)}')
+  if tuple(uv.shape) != (T, 3, 2):
+    raise ValueError(f'{name}: uv must be [{T},3,2] (three corners a face), is {tuple(uv.shape)}')
+  degrees = {(d + 1) ** 2: d for d in range(L.SHTEX_MAX_DEGREE + 1)}
+  if sh.dim() != 4 or sh.shape[3] != 3 or sh.shape[2] not in degrees or min(sh.shape[:2]) < 1 or max(sh.shape[:2]) > 2 ** 24:
+    raise ValueError(f'{name}: sh must be [Ht,Wt,K,3] with K in {sorted(degrees)} and 1 .. 2^24 texels a side, is {tuple(sh.shape)}')
+  a = L.ShtexShadeArgs()
+  a.verts, a.faces, a.n_verts, a.n_faces = verts.data_ptr(), faces.data_ptr(), V, T
+  a.face, a.bary, a.H, a.W = face.data_ptr(), bary.data_ptr(), int(face.shape[0]), int(face.shape[1])
+  a.uv, a.sh, a.Ht, a.Wt, a.degree = uv.data_ptr(), sh.data_ptr(), int(sh.shape[0]), int(sh.shape[1]), degrees[int(sh.shape[2])]
+  a.origin = (C.c_float * 3)(*finite3(name, 'origin', origin))
+  L.check(lib().mnr_shtex_shade(C.byref(a), _ptr(rgb), _stream()))
+  return rgb
+
+
 # ----------------------------------------------------------------------------- mesh geometry (csrc/meshdist.hip)
 
 # `mesh_grid_build` coarsens its cell (times 2) while the grid holds more than this many (cell, face) pairs a valid face
