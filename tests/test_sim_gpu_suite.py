@@ -59,6 +59,14 @@ def test_chain_leaf_tests_pass_on_the_simulator():
   assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail, tail
 
 
+def test_level_leaf_tests_pass_on_the_simulator():
+  """The per-ray level kernels against fp64, one gradient term at a time (tests/test_gpu_level_leaf.py): compositing forward and
+  VJP in both kernel forms, the fused and the stand-alone losses, mnr_sdist_bwd for every ray warp, render_extras, weighted_sum,
+  exposure_scale and the launchers' refusals (~15 s of simulator time on four workers)."""
+  tail = _child(['tests/test_gpu_level_leaf.py'], 900)
+  assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail, tail
+
+
 def test_sampling_gradient_kernels_pass_on_the_simulator():
   """Model.stop_level_grad = False (round 5): mnr_resample_level_bwd, mnr_cast_rays_ipe_bwd, mnr_sdist_bwd + the level kernels'
   g_x output against the oracle's autograd, and the composed train steps (at the simulator's reduced widths), with the code of
