@@ -133,7 +133,9 @@ int mnr_cast_rays_ipe_f32(const mnr_ipe_cfg* cfg, int64_t B, int n, const float*
 /* Tangent features for the density-gradient normals (models.py:478-492 via forward mode):
  * row c*B*n + s of feat_out (bf16 [3*B*n, ld_feat]) = d(IPE features of sample s)/d(mean_c), c = x,y,z, mean = the Gaussian's
  * mean as predict_density receives it (models.py:441-446: BEFORE warp_fn; with cfg->warp_contract the rows carry the
- * contraction's Jacobian and, through J cov J^T with the covariance held fixed, its derivative). */
+ * contraction's Jacobian and, through J cov J^T with the covariance held fixed, its derivative).
+ * Rows of ld_feat <= 40 are refused (three staged rows per sample would need more than 64 KiB of LDS per block), here and in
+ * mnr_ipe_from_gaussians_tangent. */
 int mnr_cast_rays_ipe_tangent(const mnr_ipe_cfg* cfg, int64_t B, int n, const float* tdist,
                               const float* origins, const float* directions, const float* radii,
                               const float* basis, uint16_t* feat_out, int ld_feat, void* stream);
@@ -555,7 +557,8 @@ int mnr_ref_head_fwd(int64_t M, int n, const float* small, const float* raw_grad
                      int col0, int col_end, float* normals_out, float* normals_pred_out, float* roughness_out, void* stream);
 /* VJP: dvi_a (+ dvi_b, may be NULL) bf16 [M, lddvi] = gradient w.r.t. the view-MLP input; g_npred / g_n
  * [M,3] fp32 from mnr_ref_losses (may be NULL).  Writes bf16 columns [0,col0) (bottleneck = dvi_a + dvi_b),
- * col_gp..+2 (predicted normals) and col_rough (roughness) of dhb [M, lddhb] and g_raw_grad [3,M] fp32 (density normals). */
+ * col_gp..+2 (predicted normals) and col_rough (roughness) of dhb [M, lddhb] and g_raw_grad [3,M] fp32 (density normals).
+ * col0 > 0 needs col0, lddvi and lddhb to be multiples of 8 (the bottleneck copy moves 16 bytes); a refused call writes nothing. */
 int mnr_ref_head_bwd(int64_t M, int n, const float* small, const float* raw_grad, const float* viewdirs,
                      const mnr_ide_tables* tabs, int features, int deg_view, float roughness_bias, const uint16_t* dvi_a,
                      const uint16_t* dvi_b, int lddvi, int col0, const float* g_npred, const float* g_n,

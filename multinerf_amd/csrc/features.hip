@@ -172,7 +172,8 @@ static int fe_launch(int mode /*0 bf16, 1 f32, 2 tangent*/, const mnr_ipe_cfg* c
   MNR_CHECK_ARG(cfg && B > 0 && n > 0 && tdist && origins && directions && radii && basis && feat_out,
                 "mnr_cast_rays_ipe: null argument");
   MNR_CHECK_ARG(cfg->ray_shape == 0 || cfg->ray_shape == 1, "ray_shape must be 'cone' or 'cylinder'");  // render.py:124
-  // (gs_launch, gaussians.hip, also refuses a block that needs more than 64 KiB of LDS; this launch never has)
+  // (fe_block_geometry also refuses a block that needs more than 64 KiB of LDS: tangent rows of ld_feat <= 40; gs_launch,
+  // gaussians.hip, refuses the same rows with the same message)
   FeGeometry geo;
   const int st = fe_block_geometry("mnr_cast_rays_ipe", "mnr_cast_rays_ipe_f32: feature count must be a multiple of 4", cfg, mode,
                                    ld_feat, &geo);

@@ -162,10 +162,7 @@ static int gs_launch(int mode /*0 bf16, 1 f32, 2 tangent*/, const char* who, con
   FeGeometry geo;                  // (fp32 rows: mnr_ipe_from_gaussians' second pass only)
   const int st = fe_block_geometry(who, "mnr_ipe_from_gaussians: feature count must be a multiple of 4 for the fp32 rows", cfg, mode,
                                    ld_feat, &geo);
-  if (st != MNR_OK) return st;
-  // (short rows: spb is capped by the thread count, not by the staging budget, and three tangent rows per sample plus their
-  // padding can pass what a launch gets without raising the dynamic-LDS limit.  fe_launch, features.hip, has no such refusal.)
-  MNR_CHECK_ARG(geo.lds <= 64 * 1024, "%s: ld_feat=%d needs %zu bytes of LDS per block (limit 65536): use a longer row", who, ld_feat, geo.lds);
+  if (st != MNR_OK) return st;         // (includes the refusal of a block that needs more than 64 KiB of LDS, as for fe_launch, features.hip)
   const dim3 grid(mnr_cdiv(M, geo.spb)), block(FE_THREADS);
   if (mode == 2) {
     hipLaunchKernelGGL((ipe_from_gaussians_kernel<false, true>), grid, block, geo.lds, (hipStream_t)stream, *cfg, M, geo.spb,
@@ -185,6 +182,9 @@ extern "C" int mnr_ipe_from_gaussians(const mnr_ipe_cfg* cfg, int64_t M, const f
                                       const float* basis, void* feat_out, int ld_feat, float* feat_f32_out, float* means_out,
                                       float* covs_out, void* stream) {
   MNR_CHECK_ARG(cfg && M > 0 && means && covs && basis && feat_out, "mnr_ipe_from_gaussians: null argument");
+  // (the second pass's own refusal, ahead of the first launch: a refused call writes nothing)
+  MNR_CHECK_ARG(!feat_f32_out || (2 * cfg->basis_k * (cfg->max_deg - cfg->min_deg)) % 4 == 0,
+                "mnr_ipe_from_gaussians: feature count must be a multiple of 4 for the fp32 rows");
   int st = gs_launch(0, "mnr_ipe_from_gaussians", cfg, M, means, covs, basis, feat_out, ld_feat, means_out, covs_out, stream);
   if (st != MNR_OK || !feat_f32_out) return st;
   // the parity-test leaf: the same features unrounded, [M, 2KL] without padding, from a second pass over the Gaussians

@@ -157,6 +157,11 @@ static inline int fe_block_geometry(const char* who, const char* f32_msg, const 
   geo->pitch = (int)row_bytes + 48;
   geo->lds = (size_t)spb * (sizeof(FeSample) + (tangent ? sizeof(FeTangent) : 0)) + (size_t)((K * 3 + 3) & ~3) * 4 +
              (size_t)spb * geo->pitch * (tangent ? 3 : 1);
+  // Short rows: spb is capped by the thread count, not by the staging budget, and three tangent rows per sample plus their
+  // padding can pass what a launch gets without raising the dynamic-LDS limit (tangent rows of ld_feat <= 40).  Refused here,
+  // for both launchers alike.
+  MNR_CHECK_ARG(geo->lds <= 64 * 1024, "%s: ld_feat=%d needs %zu bytes of LDS per block (limit 65536): use a longer row", who, ld_feat,
+                geo->lds);
   return MNR_OK;
 }
 

@@ -376,7 +376,10 @@ extern "C" int mnr_ref_head_bwd(int64_t M, int n, const float* small, const floa
   MNR_CHECK_ARG((features & MNR_REF_DENSITY_NORMALS) || !g_n, "mnr_ref_head_bwd: g_n without density-gradient normals");
   // 16-byte row pieces when the columns [col0, col0 + 8 ceil(ncols / 8)) are aligned and inside the row
   const int ncols = rf_enc_dim(features, tabs ? tabs->T : 0, deg_view) + ((features & MNR_REF_N_DOT_V) ? 1 : 0);
-  MNR_CHECK_ARG(col0 + ncols <= lddvi, "mnr_ref_head_bwd: columns out of range");
+  MNR_CHECK_ARG(col0 >= 0 && col0 + ncols <= lddvi, "mnr_ref_head_bwd: columns out of range");
+  // (the bottleneck copy behind the head kernel moves 16-byte pieces; refused here, before anything is launched)
+  MNR_CHECK_ARG(col0 == 0 || (col0 % 8 == 0 && lddvi % 8 == 0 && lddhb % 8 == 0),
+                "mnr_ref_head_bwd: bottleneck width / strides must be multiples of 8");
   const int ncol8 = (ncols + 7) / 8 * 8;
   const int vec8 = (col0 % 8 == 0 && lddvi % 8 == 0 && col0 + ncol8 <= lddvi && ((uintptr_t)dvi_a % 16) == 0 &&
                     (!dvi_b || ((uintptr_t)dvi_b % 16) == 0)) ? 1 : 0;
@@ -387,7 +390,6 @@ extern "C" int mnr_ref_head_bwd(int64_t M, int n, const float* small, const floa
                      g_raw_grad, vec8);
   MNR_CHECK_LAUNCH();
   if (col0 > 0) {
-    MNR_CHECK_ARG(col0 % 8 == 0 && lddvi % 8 == 0 && lddhb % 8 == 0, "mnr_ref_head_bwd: bottleneck width / strides must be multiples of 8");
     const int cols8 = col0 / 8;
     hipLaunchKernelGGL(ref_bottleneck_grad_kernel, dim3(mnr_cdiv(M * cols8, 256)), dim3(256), 0, (hipStream_t)stream,
                        M, cols8, (const bf16*)dvi_a, (const bf16*)dvi_b, lddvi, lddvi, (bf16*)dhb, lddhb);

@@ -106,14 +106,33 @@ def _head_ref_features(small, raw_grad, viewdirs_s, rb, F, deg, ops):
 
 
 # (predicted normals, density normals, reflect, IDE, n.v, roughness) = bits 1, 2, 4, 8, 16, 32
-@pytest.mark.parametrize('F,deg', [(63, 5), (62, 5), (47, 5), (1 | 2 | 4 | 16, 4), (1 | 2 | 4 | 16 | 32, 4), (1 | 2 | 16 | 32, 4),
-                                   (2 | 4, 3), (32, 4), (1 | 16, 2)])
-def test_ref_head_feature_sets(ops, F, deg):
-  """Every feature set the reference can run (models.py:468-563): the complete head without predicted normals (reflections about
-  the density gradient's normals), without n.v, the positional encoding of the reflection direction with and without a
-  roughness head, the view direction's encoding next to n.v, roughness as an output only ..."""
+FEATURE_SETS = [(63, 5), (62, 5), (47, 5), (1 | 2 | 4 | 16, 4), (1 | 2 | 4 | 16 | 32, 4), (1 | 2 | 16 | 32, 4), (2 | 4, 3), (32, 4), (1 | 16, 2)]
+# (col0, col_end, ld) of the view-MLP input: the 16-byte paths of both head kernels; both again with nothing behind col_end;
+# unaligned columns and an odd stride (the scalar paths; the VJP takes its bottleneck copy in 16-byte pieces and refuses
+# col0 = 3, so it runs at col0 = 0 on the same odd stride); aligned columns inside a wider row
+HEAD_LAYOUTS = [(128, 256, 256), (0, 80, 80), (3, 83, 83), (8, 96, 120)]
+HEAD_SHAPES = [(9, 16), (1, 1), (2, 129)]                    # (B, n): one sample in all; more than one block of 256
+
+
+def _head_fwd_vec8(col0, col_end, ld):
+  return col0 % 8 == 0 and col_end % 8 == 0 and ld % 8 == 0             # mnr_ref_head_fwd's condition, restated
+
+
+def _head_bwd_layout(col0, ld):
+  return (col0, ld) if col0 % 8 == 0 else (0, ld)
+
+
+def test_ref_head_layout_table_covers_every_value():
+  assert {_head_fwd_vec8(*l) for l in HEAD_LAYOUTS} == {True, False}
+  bwd = [_head_bwd_layout(c0, ld) for c0, _, ld in HEAD_LAYOUTS]
+  assert (0, 83) in bwd and any(c0 == 0 and ld % 8 == 0 for c0, ld in bwd) and any(c0 > 0 for c0, ld in bwd)
+  assert any(ce < ld for _, ce, ld in HEAD_LAYOUTS) and any(ce == ld for _, ce, ld in HEAD_LAYOUTS)
+  assert (1, 1) in HEAD_SHAPES and any(B * n > 256 for B, n in HEAD_SHAPES)
+  assert all(ce - c0 >= 74 for c0, ce, _ in HEAD_LAYOUTS)                # the widest encoding: 72 IDE columns + n.v ... and one more
+
+
+def _ref_head_feature_set(ops, F, deg, col0, col_end, ld, B, n):
   gen = torch.Generator().manual_seed(100 + F)
-  B, n = 9, 16
   M = B * n
   small = torch.randn((M, 11), generator=gen)
   raw_grad = torch.randn((3, M), generator=gen) * 3
@@ -123,8 +142,9 @@ def test_ref_head_feature_sets(ops, F, deg):
   rb = -1.0
   tabs = ops.IdeTablesDev(deg, 'cuda') if F & ops.REF_IDE else None
   has_dn, has_pn = bool(F & ops.REF_DENSITY_NORMALS), bool(F & ops.REF_PRED_NORMALS)
-  vi = torch.full((M, 256), 3.0, dtype=torch.bfloat16).cuda()
-  nrm, npred, rough = ops.ref_head_fwd(dev(small), dev(raw_grad) if has_dn else None, dev(v), n, tabs, rb, vi, 128, 256,
+  vi_buf = torch.full((M + 1, ld), 3.0, dtype=torch.bfloat16).cuda()          # (a guard row behind the matrix)
+  vi = vi_buf[:M]
+  nrm, npred, rough = ops.ref_head_fwd(dev(small), dev(raw_grad) if has_dn else None, dev(v), n, tabs, rb, vi, col0, col_end,
                                        features=F, deg_view=deg)
   s2, rg2, vs64 = small.double().requires_grad_(True), raw_grad.double().requires_grad_(True), vs.double()
   nrm_r, npred_r, rough_r, enc_r = _head_ref_features(s2, rg2, vs64, rb, F, deg, ops)
@@ -134,16 +154,20 @@ def test_ref_head_feature_sets(ops, F, deg):
       np.testing.assert_allclose(got.cpu().numpy(), want.detach().numpy(), rtol=1e-5, atol=1e-6)
   E = enc_r.shape[1]
   assert E == (2 * tabs.c.T if F & ops.REF_IDE else 3 + 6 * deg) + (1 if F & ops.REF_N_DOT_V else 0)
-  got_vi = vi.cpu().float()
-  np.testing.assert_allclose(got_vi[:, 128:128 + E].numpy(), enc_r.detach().numpy(), rtol=2**-7, atol=2e-3)
-  assert (got_vi[:, :128] == 3.0).all() and (got_vi[:, 128 + E:] == 0.0).all()
+  got_vi = vi_buf.cpu().float()
+  np.testing.assert_allclose(got_vi[:M, col0:col0 + E].numpy(), enc_r.detach().numpy(), rtol=2**-7, atol=2e-3)
+  assert (got_vi[:M, :col0] == 3.0).all() and (got_vi[:M, col0 + E:col_end] == 0.0).all()
+  assert (got_vi[:M, col_end:] == 3.0).all() and (got_vi[M] == 3.0).all()   # columns behind col_end and the guard row: untouched
 
+  bcol0, bld = _head_bwd_layout(col0, ld)
   g_enc = torch.randn((M, E), generator=gen) * 0.1
   g_np_l = torch.randn((M, 3), generator=gen) * 0.1 if has_pn else None
   g_n_l = torch.randn((M, 3), generator=gen) * 0.1 if has_dn else None
-  dvi_a = torch.zeros((M, 256), dtype=torch.bfloat16)
-  dvi_a[:, 128:128 + E] = g_enc.to(torch.bfloat16)
-  g_used = dvi_a[:, 128:128 + E].double()
+  dvi_a = torch.zeros((M, bld), dtype=torch.bfloat16)
+  dvi_a[:, :bcol0] = torch.randn((M, bcol0), generator=gen).to(torch.bfloat16)   # the bottleneck part: copied into dhb as it is
+  dvi_a[:, bcol0 + E:] = torch.randn((M, bld - bcol0 - E), generator=gen).to(torch.bfloat16)      # columns no head kernel may read
+  dvi_a[:, bcol0:bcol0 + E] = g_enc.to(torch.bfloat16)
+  g_used = dvi_a[:, bcol0:bcol0 + E].double()
   obj = (enc_r * g_used).sum()
   if has_pn:
     obj = obj + (npred_r * g_np_l.double()).sum()
@@ -151,14 +175,17 @@ def test_ref_head_feature_sets(ops, F, deg):
     obj = obj + (nrm_r * g_n_l.double()).sum()
   if obj.requires_grad:
     obj.backward()
-  dhb = torch.full((M, 256), 7.0, dtype=torch.bfloat16).cuda()
-  g_rg = ops.ref_head_bwd(dev(small), dev(raw_grad) if has_dn else None, dev(v), n, tabs, rb, dev(dvi_a), None, 128,
+  dhb_buf = torch.full((M + 1, 256), 7.0, dtype=torch.bfloat16).cuda()
+  dhb = dhb_buf[:M]
+  g_rg = ops.ref_head_bwd(dev(small), dev(raw_grad) if has_dn else None, dev(v), n, tabs, rb, dev(dvi_a), None, bcol0,
                           dev(g_np_l) if has_pn else None, dev(g_n_l) if has_dn else None, dhb, 129, 138, features=F, deg_view=deg)
   assert (g_rg is None) == (not has_dn)
   if has_dn:
     want = rg2.grad.numpy() if rg2.grad is not None else np.zeros((3, M))
     np.testing.assert_allclose(g_rg.cpu().numpy(), want, rtol=1e-4, atol=1e-6 * max(1.0, float(np.abs(want).max())))
-  got = dhb.cpu().float()
+  got = dhb_buf.cpu().float()
+  assert (got[M] == 7.0).all()
+  got = got[:M]
   sg = s2.grad if s2.grad is not None else torch.zeros_like(s2)
   if has_pn:
     ref_gp = sg[:, 1:4]
@@ -173,6 +200,41 @@ def test_ref_head_feature_sets(ops, F, deg):
   else:
     assert (got[:, 138] == 7.0).all()
   assert (got[:, 132:138] == 7.0).all()
+  assert torch.equal(got[:, :bcol0], dvi_a[:, :bcol0].float())          # the bottleneck copy, bit for bit
+  assert (got[:, bcol0:129] == 7.0).all() and (got[:, 139:] == 7.0).all()
+
+
+@pytest.mark.parametrize('F,deg', FEATURE_SETS)
+def test_ref_head_feature_sets(ops, F, deg):
+  """Every feature set the reference can run (models.py:468-563): the complete head without predicted normals (reflections about
+  the density gradient's normals), without n.v, the positional encoding of the reflection direction with and without a
+  roughness head, the view direction's encoding next to n.v, roughness as an output only ..."""
+  _ref_head_feature_set(ops, F, deg, *HEAD_LAYOUTS[0], *HEAD_SHAPES[0])
+
+
+@pytest.mark.parametrize('F,deg,col0,col_end,ld,B,n', [fs + lay + sh for fs in FEATURE_SETS for lay in HEAD_LAYOUTS for sh in HEAD_SHAPES
+                                                       if (lay, sh) != (HEAD_LAYOUTS[0], HEAD_SHAPES[0])])
+def test_ref_head_feature_sets_at_other_layouts(ops, F, deg, col0, col_end, ld, B, n):
+  """The same at every other column layout and shape of the tables above."""
+  _ref_head_feature_set(ops, F, deg, col0, col_end, ld, B, n)
+
+
+def test_ref_head_bwd_refuses_before_it_launches(ops):
+  """A bottleneck width that the 16-byte copy cannot take (col0 = 5) is refused before the head kernel is launched: dhb and
+  g_raw_grad keep their sentinels."""
+  import ctypes as C
+  M, n = 32, 16
+  small, rg, v = torch.randn((M, 11)).cuda(), torch.randn((3, M)).cuda(), torch.ones((2, 3)).cuda()
+  dvi = torch.zeros((M, 96), dtype=torch.bfloat16).cuda()
+  dhb = torch.full((M, 256), 7.0, dtype=torch.bfloat16).cuda()
+  g_rg = torch.full((3, M), 7.0).cuda()
+  F = ops.REF_PRED_NORMALS | ops.REF_DENSITY_NORMALS | ops.REF_N_DOT_V
+  p = ops._ptr
+  with pytest.raises(ValueError, match='bottleneck width / strides must be multiples of 8'):
+    ops.L.check(ops.lib().mnr_ref_head_bwd(M, n, p(small), p(rg), p(v), None, F, 4, 0.0, p(dvi), None, 96, 5, None, None, p(dhb), 256, 129, 138,
+                                           p(g_rg), ops._stream()))
+  torch.cuda.synchronize()
+  assert (dhb.float().cpu() == 7.0).all() and (g_rg.cpu() == 7.0).all()
 
 
 def test_ref_head_refuses_what_the_reference_cannot_run(ops):

@@ -67,6 +67,14 @@ def test_level_leaf_tests_pass_on_the_simulator():
   assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail, tail
 
 
+def test_ipe_leaf_tests_pass_on_the_simulator():
+  """The featurisation kernels against fp64 at free shapes (tests/test_gpu_ipe_leaf.py): fp32, bf16 and tangent rows of rays and
+  of caller-supplied Gaussians per degree, both VJPs with respect to the interval ends, the two view-direction kernels, the GLO
+  kernels, the edge inputs and the launchers' refusals (~25 s of simulator time on four workers)."""
+  tail = _child(['tests/test_gpu_ipe_leaf.py'], 900)
+  assert ' passed' in tail and 'failed' not in tail and 'skipped' not in tail, tail
+
+
 def test_sampling_gradient_kernels_pass_on_the_simulator():
   """Model.stop_level_grad = False (round 5): mnr_resample_level_bwd, mnr_cast_rays_ipe_bwd, mnr_sdist_bwd + the level kernels'
   g_x output against the oracle's autograd, and the composed train steps (at the simulator's reduced widths), with the code of
