@@ -5,10 +5,17 @@ The mesh is a PLY that `mesh.write_ply` wrote (extract_mesh.py's output): with p
 PNG its `comment TextureFile` line names (looked up next to the file), otherwise with its vertex colours, otherwise as shaded
 normals.  Where the header also names a `comment TextureSH` file (extract_mesh.py --texture_sh) and it lies next to the mesh, every
 pixel is shaded with the texel's spherical harmonics at its own view direction (`ops.shtex_shade`, csrc/shtex.hip), and the script
-says so; --no_view_dependent scores the plain texture instead.  Every view is rasterised on the device (`mesh.render_mesh`,
-csrc/raster.hip) and scored by `image.MetricHarness` (PSNR and SSIM), honouring Config.eval_quantize_metrics and
-Config.eval_crop_borders as eval.py does.  No checkpoint is needed.  Perspective cameras only: a dataset whose cameras
-`mesh.world_to_pixel` refuses (lens distortion, NDC rays, fisheye) fails with its message.
+says so; --no_view_dependent scores the plain texture instead.  Every view is rendered on the device (`mesh.render_mesh`) and scored
+by `image.MetricHarness` (PSNR and SSIM), honouring Config.eval_quantize_metrics and Config.eval_crop_borders as eval.py does.  No
+checkpoint is needed.
+
+--method auto|raster|raycast (default auto).  `raster` is the rasteriser (csrc/raster.hip), for undistorted pinhole cameras only: a
+dataset whose cameras `mesh.world_to_pixel` refuses fails with its message.  `raycast` casts the dataset's own ray of every pixel at
+the mesh (csrc/meshray.hip) and so renders any camera model: lens distortion, a fisheye camtype, an NDC ray space (the rays are taken
+in world space, before the NDC conversion) and the spherical 'pano' render camera.  `auto` rasterises a pinhole dataset, with every
+output file byte for byte what `raster` writes, and casts rays otherwise; the script prints which method the run used.  A render
+path (Config.render_path = True, the only way to a Config.render_camtype) has no images to score: its views are rendered and
+written, and the metric files are left out.
 
 Under --out_dir (default: <mesh file's directory>/mesh_eval) it writes mesh_color_NNN.png for every view and, in eval.py's format
 (one line, values separated by blanks), mesh_metric_psnr.txt, mesh_metric_ssim.txt and mesh_render_times.txt (seconds a view:
@@ -61,6 +68,8 @@ def parse_args(argv):
   ap.add_argument('--near', type=float, default=None, help='surface nearer than this (zc) is not seen; default: Config.near')
   ap.add_argument('--bg', default='1,1,1', help='r,g,b of the pixels no face covers')
   ap.add_argument('--cull', choices=('none', 'back'), default='none')
+  ap.add_argument('--method', choices=('auto', 'raster', 'raycast'), default='auto',
+                  help='rasterise (pinhole cameras only), cast rays (any camera model), or choose by the dataset\'s cameras')
   ap.add_argument('--no_view_dependent', action='store_true',
                   help='score the plain texture although the mesh names a `comment TextureSH` file (spherical harmonics per texel)')
   ap.add_argument('--gt_mesh', default=None, help='a ground-truth PLY (mesh or point cloud): score the geometry against it')
@@ -208,23 +217,43 @@ def main(argv=None):
   n = min(dataset.size, config.eval_dataset_limit)
   psnrs, ssims, seconds = [], [], []
   from PIL import Image
+  method = args.method
+  if method == 'auto':
+    method = 'raster' if mesh.camera_is_pinhole(dataset.distortion_params, dataset.pixtocam_ndc, camtype) else 'raycast'
+  print(f'rendering method: {method}' + (' (chosen by the cameras)' if args.method == 'auto' else ''))
+  score = not dataset.render_path
+  if not score:
+    print('a render path has no images: the views are rendered and written, not scored')
   for idx in range(n):
-    proj = mesh.world_to_pixel(pixtocams if pixtocams.ndim == 2 else pixtocams[idx], dataset.camtoworlds[idx],
-                               distortion_params=dataset.distortion_params, pixtocam_ndc=dataset.pixtocam_ndc, camtype=camtype)
+    ptc = pixtocams if pixtocams.ndim == 2 else pixtocams[idx]
+    kw = dict(texture=texture, colors=colors, near=near, bg=args.bg, cull=args.cull, supersample=args.supersample,
+              view_dependent=not args.no_view_dependent)
+    if method == 'raster':
+      proj = mesh.world_to_pixel(ptc, dataset.camtoworlds[idx], distortion_params=dataset.distortion_params, pixtocam_ndc=dataset.pixtocam_ndc,
+                                 camtype=camtype)
     torch.cuda.synchronize()
     t0 = time.time()
-    r = mesh.render_mesh(dm, None, None, dataset.height, dataset.width, texture=texture, colors=colors, near=near, bg=args.bg, cull=args.cull,
-                         supersample=args.supersample, proj=proj, view_dependent=not args.no_view_dependent)
+    if method == 'raster':
+      r = mesh.render_mesh(dm, None, None, dataset.height, dataset.width, proj=proj, **kw)
+    else:
+      r = mesh.render_mesh(dm, ptc, dataset.camtoworlds[idx], dataset.height, dataset.width, method='raycast',
+                           distortion_params=dataset.distortion_params, pixtocam_ndc=dataset.pixtocam_ndc, camtype=camtype, **kw)
     torch.cuda.synchronize()
     seconds.append(time.time() - t0)
-    gt = torch.as_tensor(dataset.images[idx]).to(device=dev, dtype=torch.float32)[..., :3].contiguous()
-    metric = harness(r['rgb'].contiguous(), gt, quantize=quant, crop=crop)
-    psnrs.append(metric['psnr'])
-    ssims.append(metric['ssim'])
-    print(f'Mesh image {idx + 1}/{n}: {seconds[-1]:.4f}s, psnr {metric["psnr"]:.3f}, ssim {metric["ssim"]:.4f}', flush=True)
+    if score:
+      gt = torch.as_tensor(dataset.images[idx]).to(device=dev, dtype=torch.float32)[..., :3].contiguous()
+      metric = harness(r['rgb'].contiguous(), gt, quantize=quant, crop=crop)
+      psnrs.append(metric['psnr'])
+      ssims.append(metric['ssim'])
+      print(f'Mesh image {idx + 1}/{n}: {seconds[-1]:.4f}s, psnr {metric["psnr"]:.3f}, ssim {metric["ssim"]:.4f}', flush=True)
+    else:
+      print(f'Mesh image {idx + 1}/{n}: {seconds[-1]:.4f}s', flush=True)
     Image.fromarray(to_u8(r['rgb'])).save(os.path.join(out_dir, f'mesh_color_{idx:03d}.png'))
-  print(f'Average mesh psnr over {n} images: {np.mean(psnrs):.3f}, ssim {np.mean(ssims):.4f}')
-  for name, values in (('mesh_metric_psnr.txt', psnrs), ('mesh_metric_ssim.txt', ssims), ('mesh_render_times.txt', seconds)):
+  files = [('mesh_render_times.txt', seconds)]
+  if score:
+    print(f'Average mesh psnr over {n} images: {np.mean(psnrs):.3f}, ssim {np.mean(ssims):.4f}')
+    files = [('mesh_metric_psnr.txt', psnrs), ('mesh_metric_ssim.txt', ssims)] + files
+  for name, values in files:
     with open(os.path.join(out_dir, name), 'w') as f:
       f.write(' '.join(str(v) for v in values))
   if args.gt_mesh:

@@ -1359,6 +1359,8 @@ int mnr_shtex_shade(const mnr_shtex_shade_args* args, float* rgb, void* stream);
 #define MNR_MESHDIST_MAX_DIM 1024
 #define MNR_MESHDIST_MARGIN 0.03125f            /* 2^-5 of a cell */
 #define MNR_MESHDIST_SHRINK 0.9999847412109375f /* 1 - 2^-16 */
+#define MNR_MESHRAY_MARGIN 0.03125f              /* 2^-5 of a cell: the ray caster's walk ("Mesh ray casting" below) */
+#define MNR_MESHRAY_REL 3.814697265625e-06f      /* 2^-18 = 64 float32 ulps, of R (there) */
 typedef struct {
   const float* verts;              /* [n_verts,3] */
   const int* faces;                /* [n_faces,3] */
@@ -1429,6 +1431,65 @@ int mnr_icp_sums(int64_t n, const float* p, const float* x, const float* nrm, co
                  double* out, void* stream);
 int mnr_crop_polygon(const float* points, int64_t n, const double* polygon, int m, int axis, double w_min, double w_max, uint8_t* keep,
                      void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * Mesh ray casting: the nearest ray-triangle intersection over the grid of "Mesh geometry", and its shading  (csrc/meshray.hip)
+ * The notation, the validity of a face, cell() and the grid (mnr_mesh_grid_count / mnr_mesh_grid_fill, the caller's sort and cell_start)
+ * are those of "Mesh geometry" above.  float32 in the order written unless it says float64, no contraction; tests/raycast_ref.py
+ * restates the hit test and the resolve in NumPy, every ray against every face, with no grid.
+ *
+ * Hit test of a ray (o, d) and a face (a, b, c), the watertight test of Woop, Benthin and Wald (2013); it knows nothing of the grid.
+ *   Per ray.   kz = the axis of the largest |d_k| (the lowest index among equal magnitudes);  kx = kz + 1 mod 3, ky = kx + 1 mod 3,
+ *              exchanged if d_kz < 0.  Sx = d_kx / d_kz,  Sy = d_ky / d_kz,  Sz = 1 / d_kz.
+ *   Per corner.  A = a - o;  Ax = A_kx - Sx A_kz,  Ay = A_ky - Sy A_kz,  Az = Sz A_kz  (the product first);  B and C likewise.
+ *   Edge functions, in FLOAT64 from those float32 numbers converted exactly:  U = Cx By - Cy Bx,  V = Ax Cy - Ay Cx,  W = Bx Ay - By Ax.
+ *              Each product is exact in float64 and each difference is rounded once, so each sign is exact for the sheared corners.
+ *   Inside     iff not ((U < 0 or V < 0 or W < 0) and (U > 0 or V > 0 or W > 0)): no two have strictly opposite signs, zeros count as
+ *              inside;  and det = (U + V) + W is not 0 (a NaN is not 0 here and fails below).  With cull = MNR_RASTER_CULL_BACK also
+ *              det > 0: the FRONT faces, whose corners run counter-clockwise seen from the ray origin, i.e. whose geometric normal
+ *              (b - a) x (c - a) has a negative product with d: the rasteriser's `front`.
+ *   t = float32(((U Az + V Bz) + W Cz) / det)  (float64, Az .. Cz converted exactly, rounded to float32 once).
+ *   ELIGIBLE   iff the face is valid, inside, t_min < t <= t_max with t finite (t_max = +inf: no upper limit; a t of +inf or NaN is
+ *              never eligible), and the face has AREA: n = cross(b - a, c - a), evaluated in float64 from the corners converted first
+ *              (mnr_mesh_face_areas' n), is not (0, 0, 0).  bary = (float32(U / det), float32(V / det), float32(W / det)).
+ *   Two faces that share an edge compute the same two sheared corners, so the ray lies on opposite sides of the edge for them, or on it
+ *   for both: it is hit by both and never by neither.  Why the area clause: two equal corners give det = 0 for every ray (one edge
+ *   function is 0, the other two cancel exactly), but the sheared images of three collinear corners are collinear to rounding only, and
+ *   a test that is exact for the sheared corners sees a sliver of that width and lets a ray aimed at it pass.  A face without area in
+ *   its own float32 corners is therefore never hit by the clause, not by det; a sliver that has area is a face like any other.
+ *   Directions are NOT normalised: t is in units of |d|.
+ *
+ * Result per ray: the minimum of key = (bits(t) << 32) | face over the eligible faces of the WHOLE mesh (t > t_min >= 0: its bit pattern is
+ * monotone; the rasteriser's and the distance query's resolve): t [n] float32, face [n] int32 the lowest id among the nearest hits, bary
+ * [n,3] float32 of that face.  No eligible face, a ray with a component of o or d that is not finite, d = 0, or a 1 / d_kz that is not finite:
+ * t = +inf, face = -1, bary = 0.  The result does not depend on the grid, the traversal or the order of the rays: two runs, two grids and a
+ * permuted batch agree bit for bit.
+ *
+ * mnr_mesh_raycast, one thread a ray; with `order` [n] (int64, or NULL) thread i serves ray order[i], as in mnr_mesh_distance.  The walk:
+ *   R = 2 max_a max(|o_a|, |origin_a|, |hi_a|);  w = MNR_MESHRAY_MARGIN cell + MNR_MESHRAY_REL R;  wt = min(w |Sz|, FLT_MAX).
+ *   Slabs.  c_0 = o_kz + t_min d_kz, c_1 = o_kz + t_max d_kz;  the slabs s (cell index on axis kz) from cell(min(c_0, c_1) - 2 w) to
+ *     cell(max(c_0, c_1) + 2 w), none if that range lies outside the grid; in ascending order if d_kz > 0, else descending.
+ *   Per slab.  zlo = (origin_kz + float(s) cell) - w,  zhi = (origin_kz + float(s + 1) cell) + w;  ta = (zlo - o_kz) Sz, tb = (zhi - o_kz) Sz,
+ *     exchanged if d_kz < 0;  ta = max(ta, t_min) - wt,  tb = min(tb, t_max) + wt.  On each of the axes a = kx, ky:  p = o_a + ta d_a,
+ *     p' = o_a + tb d_a (o_a where d_a == 0), the cells cell((min(p, p') - w)) .. cell((max(p, p') + w)), none if that range lies outside
+ *     the grid.  Every face of every cell of that rectangle is tested.
+ *   Stop after slab s when  best t < tn - 2 wt,  tn = (z - o_kz) Sz with z the plane between slab s and the next one in the ray's
+ *     direction.  csrc/meshray.hip argues why no face not yet seen can then have a key at or below the best one.
+ *   The slab index advances by one an iteration, at most MNR_MESHDIST_MAX_DIM times.  cell_start entries outside [0, n_pairs], pair_face
+ *   entries outside [0, n_faces), face indices outside the vertices and entries of order outside [0, n) are skipped: no access leaves
+ *   the inputs.  t_min >= 0 and finite, t_max > t_min.  n == 0 launches nothing; n_pairs == 0: every ray gets the empty result.
+ *
+ * mnr_raycast_shade, one thread a ray i of n, reads face [n] and bary [n,3] and, of `args`, the mesh (verts, normals, faces), colors or
+ * texture + uv, and bg (proj, H, W, near, cull and threshold are not read).  For 0 <= face < n_faces with its three indices inside the
+ * vertices, with l = bary: normals [n,3] and rgb [n,3] exactly as mnr_raster_shade writes them from l (the interpolated normal with
+ * its two fallbacks; colors, texture or the shaded normal), the same operations in the same order, so equal (face, bary) give equal
+ * bits.  Any other ray: normals 0, rgb = bg.
+ * ------------------------------------------------------------------------- */
+int mnr_mesh_raycast(const mnr_meshdist_args* args, const int64_t* cell_start, const int* pair_face, int64_t n_pairs,
+                     const float* origins, const float* directions, const int64_t* order, int64_t n, float t_min, float t_max, int cull,
+                     float* t, int* face, float* bary, void* stream);
+int mnr_raycast_shade(const mnr_raster_args* args, const int* face, const float* bary, int64_t n, float* normals, float* rgb,
+                      void* stream);
 
 #ifdef __cplusplus
 }

@@ -388,6 +388,8 @@ _PROTOS = {
     'mnr_icp_sums_partials': ([i64], i32),
     'mnr_icp_sums': ([i64, vp, vp, vp, vp, C.POINTER(C.c_double), vp, vp, vp], i32),
     'mnr_crop_polygon': ([vp, i64, vp, i32, i32, C.c_double, C.c_double, vp, vp], i32),
+    'mnr_mesh_raycast': ([C.POINTER(MeshDistArgs), vp, vp, i64, vp, vp, vp, i64, f32, f32, i32, vp, vp, vp, vp], i32),
+    'mnr_raycast_shade': ([C.POINTER(RasterArgs), vp, vp, i64, vp, vp, vp], i32),
     'mnr_weight_decay': ([vp, i64, i64, f32, vp, vp, vp, vp], i32),
     'mnr_grad_sqnorm': ([vp, i64, i64, f32, vp, vp], i32),
     'mnr_clip_adam': ([C.POINTER(AdamCfg), i64, i64, vp, vp, vp, vp, vp, vp], i32),

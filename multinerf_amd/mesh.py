@@ -11,7 +11,9 @@
   simplify       vertex clustering on a coarser grid with quadric-error placement (csrc/meshclean.hip)
   bake_texture   a texture atlas of per-face charts, every texel queried with its own footprint's Gaussian (csrc/atlas.hip)
   write_obj      OBJ + MTL + PNG of a mesh with a baked texture (write_ply takes the texture too)
-  render_mesh    rasterise a mesh from a camera: face ids, depth, barycentrics, normals, colour (csrc/raster.hip)
+  render_mesh    a mesh seen by a camera: face ids, depth, barycentrics, normals, colour; rasterised (csrc/raster.hip) for a pinhole,
+                 ray cast (csrc/meshray.hip) for any camera model: lens distortion, fisheye, NDC datasets, panoramas
+  cast_rays      what does this ray hit: the nearest intersection of free rays with a mesh (csrc/meshray.hip)
   sample_surface / point_mesh_distance / geometry_metrics   area-stratified surface samples, the distance of points to a mesh or
                  point cloud, and accuracy, completeness, Chamfer and F-score against a ground truth (csrc/meshdist.hip)
   closest_points / CropVolume / register   the closest point and normal on a mesh, Tanks and Temples' polygonal crop volumes, and
@@ -156,6 +158,13 @@ def world_to_pixel(pixtocam, camtoworld, distortion_params=None, pixtocam_ndc=No
   R, o = c2w[:, :3], c2w[:, 3]
   w2c = np.concatenate([R.T, -(R.T @ o)[:, None]], 1)
   return np.ascontiguousarray(K @ np.diag([1., -1., -1.]) @ w2c, dtype=np.float32)
+
+
+def camera_is_pinhole(distortion_params=None, pixtocam_ndc=None, camtype=camera_utils.ProjectionType.PERSPECTIVE):
+  """True iff `world_to_pixel` accepts the camera model: no lens distortion, no NDC ray space, neither fisheye nor 'pano'."""
+  if distortion_params is not None or pixtocam_ndc is not None or (isinstance(camtype, str) and camtype == 'pano'):
+    return False
+  return camera_utils.ProjectionType(camtype) == camera_utils.ProjectionType.PERSPECTIVE
 
 
 # the 7 edge directions of csrc/mesh.hip, by edge number
@@ -570,7 +579,8 @@ def projection_origin(proj):
 
 
 def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=None, near=0.05, bg=(1., 1., 1.), cull='none', supersample=1,
-                proj=None, threshold=None, view_dependent=True, origin=None):
+                proj=None, threshold=None, view_dependent=True, origin=None, method='raster', distortion_params=None, pixtocam_ndc=None,
+                camtype=camera_utils.ProjectionType.PERSPECTIVE):
   """The mesh dict `m` (vertices, normals, faces on the device) seen by a perspective camera, rasterised on the device
   (ops.raster_visibility + ops.raster_shade, csrc/raster.hip; include/mnerf.h states the contract): dict(rgb [H,W,3], acc [H,W],
   face [h,w] int32, depth [h,w], bary [h,w,3], normals [h,w,3], proj [3,4] the host matrix that was rendered) of device tensors, float32
@@ -594,11 +604,32 @@ def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=Non
   is converted to float32 once) is VIEW-DEPENDENT: after the shading pass, ops.shtex_shade (csrc/shtex.hip) overwrites rgb, where a
   face is hit, with the texel's spherical harmonics evaluated at the unit direction from `origin` to the pixel's surface point.
   origin defaults to the eye: camtoworld[:3, 3], or with proj= `projection_origin(proj)`.  view_dependent=False, or a dict without
-  sh, renders the plain texture exactly as before.  Supersampling follows either."""
+  sh, renders the plain texture exactly as before.  Supersampling follows either.
+
+  method = 'raster' (the default) is the above; a camera that `world_to_pixel` refuses (distortion_params, pixtocam_ndc, a fisheye or
+  'pano' camtype) fails with its message.  method = 'raycast' renders ANY camera model by casting the ray of every pixel centre at
+  the mesh (ops.mesh_raycast + ops.raycast_shade, csrc/meshray.hip), then ops.shtex_shade as above.  The rays are the model's own,
+  built on the device: camera_utils.pixels_to_rays for a perspective or fisheye `camtype`, with or without `distortion_params`, and
+  ops.spherical_rays for camtype = 'pano'; pixtocam and camtoworld are needed (proj= is refused), the origin is the camera's eye.  It
+  returns the same dict with proj = None: depth is t, the ray parameter of the hit in units of the length of `directions`, which is
+  the distance a model renders along those rays for every camera type and equals zc for a pinhole (0 where nothing is hit, as
+  above); acc is 1 on a hit; only surface with t > near is seen; cull is the same `front`.  supersample = k casts k x k rays a pixel:
+  pixtocam diag(1 / k, 1 / k, 1) at k height x k width (a panorama is simply rendered at k height x k width).  With `pixtocam_ndc` the
+  rays are taken BEFORE the NDC conversion, because the mesh lives in world space: depth is then the world-space ray parameter and
+  NOT the distance the model renders in its NDC ray space.  method = 'auto' rasterises where `camera_is_pinhole` and casts rays
+  otherwise."""
   height, width, k = int(height), int(width), int(supersample)
   if height < 1 or width < 1 or k < 1:
     raise ValueError(f'render_mesh: height = {height}, width = {width} and supersample = {k} must be at least 1')
-  P = np.array(world_to_pixel(pixtocam, camtoworld) if proj is None else _host(proj, np.float32).reshape(3, 4), dtype=np.float32)
+  if method not in ('raster', 'raycast', 'auto'):
+    raise ValueError(f"render_mesh: method = {method!r} must be 'raster', 'raycast' or 'auto'")
+  if method == 'auto':
+    method = 'raster' if camera_is_pinhole(distortion_params, pixtocam_ndc, camtype) else 'raycast'
+  if method == 'raycast':
+    return _render_mesh_raycast(m, pixtocam, camtoworld, height, width, texture, colors, near, bg, cull, k, proj, view_dependent, origin,
+                                distortion_params, camtype)
+  P = np.array(world_to_pixel(pixtocam, camtoworld, distortion_params, pixtocam_ndc, camtype) if proj is None else
+               _host(proj, np.float32).reshape(3, 4), dtype=np.float32)
   use_sh = bool(view_dependent) and texture is not None and texture.get('sh') is not None
   if use_sh and origin is None:
     origin = _host(camtoworld, np.float64)[..., :3, 3].reshape(3) if proj is None else projection_origin(proj)
@@ -628,6 +659,75 @@ def render_mesh(m, pixtocam, camtoworld, height, width, texture=None, colors=Non
     out['acc'] = out['acc'].reshape(height, k, width, k).mean((1, 3))
   out['proj'] = P
   return out
+
+
+def _render_mesh_raycast(m, pixtocam, camtoworld, height, width, texture, colors, near, bg, cull, k, proj, view_dependent, origin,
+                         distortion_params, camtype):
+  """render_mesh(method='raycast'): its docstring says what this does."""
+  if proj is not None or pixtocam is None or camtoworld is None:
+    raise ValueError("render_mesh: method = 'raycast' builds the camera's rays: it needs pixtocam and camtoworld and takes no proj")
+  pano = isinstance(camtype, str) and camtype == 'pano'
+  if not pano:
+    camtype = camera_utils.ProjectionType(camtype)
+  h, w = k * height, k * width
+  dm = _device_mesh(m)
+  dev = dm['vertices'].device
+  c2w = torch.as_tensor(_host(camtoworld, np.float32)[..., :3, :4].reshape(3, 4)).to(dev)
+  if pano:
+    origins, directions = ops.spherical_rays(c2w, h, w)[:2]
+  else:
+    ptc = _host(pixtocam, np.float64).reshape(3, 3) @ np.diag([1. / k, 1. / k, 1.])
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.int32, device=dev), torch.arange(w, dtype=torch.int32, device=dev), indexing='ij')
+    origins, directions = camera_utils.pixels_to_rays(xs, ys, torch.as_tensor(ptc, dtype=torch.float32).to(dev), c2w,
+                                                      distortion_params=distortion_params, camtype=camtype)[:2]
+  use_sh = bool(view_dependent) and texture is not None and texture.get('sh') is not None
+  if origin is None:
+    origin = _host(camtoworld, np.float64)[..., :3, 3].reshape(3)
+  if colors is True:
+    colors = m.get('colors')
+  kw = dict(colors=None if colors is None else torch.as_tensor(colors).to(dev).contiguous())
+  if texture is not None:
+    kw.update(texture=torch.as_tensor(texture['texture']).to(dev).contiguous(), uv=torch.as_tensor(texture['uv']).to(device=dev, dtype=torch.float32).contiguous())
+  t, face, bary = ops.mesh_raycast(origins.reshape(-1, 3).contiguous(), directions.reshape(-1, 3).contiguous(), dm['vertices'], dm['faces'],
+                                   t_min=ops.positive_f32('render_mesh', 'near', near), cull=cull, order=ops.pixel_tile_order(h, w, dev))
+  face, bary = face.reshape(h, w), bary.reshape(h, w, 3)
+  out = ops.raycast_shade(dm, face, bary, bg=[float(v) for v in bg], **kw)
+  if use_sh:
+    sh = torch.as_tensor(texture['sh']).to(device=dev, dtype=torch.float32).contiguous()
+    ops.shtex_shade(dm, face, bary, kw['uv'], sh, origin, out['rgb'])
+  hit = face >= 0
+  out.update(face=face, bary=bary, acc=hit.to(torch.float32), depth=torch.where(hit, t.reshape(h, w), torch.zeros((), dtype=torch.float32, device=dev)))
+  if k > 1:
+    out['rgb'] = out['rgb'].reshape(height, k, width, k, 3).mean((1, 3))
+    out['acc'] = out['acc'].reshape(height, k, width, k).mean((1, 3))
+  out['proj'] = None
+  return out
+
+
+def cast_rays(m, origins, directions, t_min=0., t_max=None, cull='none', grid=None):
+  """What does this ray hit?  dict(t [..] float32, face [..] int32, bary [..,3], points [..,3], normals [..,3] float32) of the rays
+  origins + t directions ([..,3] each, tensors or host arrays; directions are NOT normalised and t is in units of their length) against
+  the mesh dict `m` (vertices and faces, tensors or host arrays), in the rays' leading shape: the nearest intersection with
+  t_min < t <= t_max (ops.mesh_raycast, csrc/meshray.hip; include/mnerf.h states the watertight hit test), the face that is hit (the
+  lowest id among equally near ones), the barycentrics of the hit on it, the point origins + t directions and the face's unit normal
+  (b - a) x (c - a) / |.| (ops.mesh_face_normals; it does not depend on the side the ray comes from).  cull = 'back' ignores faces seen
+  from behind.  On a miss: t = +inf, face = -1, bary and normals 0, and points is not finite.  `grid` is ops.mesh_grid_build's for a
+  caller that casts many batches at one mesh.  t_max is the primitive of an occlusion test: a ray towards a point at parameter 1 is
+  blocked iff it hits something with t_max just below 1."""
+  verts, faces = _shape(m)
+  o = torch.as_tensor(origins).to(device=verts.device, dtype=torch.float32)
+  d = torch.as_tensor(directions).to(device=verts.device, dtype=torch.float32)
+  if o.dim() < 1 or o.shape[-1] != 3 or o.shape != d.shape:
+    raise ValueError(f'cast_rays: origins and directions must be [..,3] of one shape, are {tuple(o.shape)} and {tuple(d.shape)}')
+  lead = tuple(o.shape[:-1])
+  o, d = o.reshape(-1, 3).contiguous(), d.reshape(-1, 3).contiguous()
+  t, face, bary = ops.mesh_raycast(o, d, verts, faces, t_min=t_min, t_max=t_max, cull=cull, grid=grid)
+  hit = face >= 0
+  normals = torch.zeros_like(o)
+  if faces.shape[0] > 0:
+    normals = torch.where(hit[:, None], ops.mesh_face_normals(verts, faces)[face.long().clamp(min=0)], normals)
+  return dict(t=t.reshape(lead), face=face.reshape(lead), bary=bary.reshape(lead + (3,)), points=(o + t[:, None] * d).reshape(lead + (3,)),
+              normals=normals.reshape(lead + (3,)))
 
 
 def _host(x, dtype):

@@ -1977,19 +1977,9 @@ def raster_visibility(m, proj, height, width, near, cull='none', threshold=None,
   return vis
 
 
-def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1., 1., 1.)):
-  """dict(face [H,W] int32, depth [H,W], acc [H,W], bary [H,W,3], normals [H,W,3], rgb [H,W,3] float32) of a visibility buffer `vis`
-  [H,W] int64 that `raster_visibility` wrote for the same mesh, projection and near (mnr_raster_shade; include/mnerf.h): the winning
-  face (-1: none), its zc, 1 where there is one, the perspective-correct barycentrics, the interpolated unit normal and the colour:
-  `colors` [V,3] uint8 or float32 blended over the face, or `texture` [Ht,Wt,3] uint8 or float32 looked up bilinearly at the blend of
-  `uv` [T,3,2] (per face corner, v = 1 the top row: what mesh.bake_texture returns), or, with neither, 0.5 + 0.5 normal.  Pixels
-  without a face get `bg`."""
-  name = 'raster_shade'
-  _chk(vis, torch.int64, f'{name}: vis')
-  if vis.dim() != 2:
-    raise ValueError(f'{name}: vis must be [H,W], is {tuple(vis.shape)}')
-  H, W = int(vis.shape[0]), int(vis.shape[1])
-  a, keep = _raster_args(name, m, proj, H, W, near)
+def _shade_colour_args(name, a, colors, texture, uv, bg):
+  """Set the colour source and the background of the RasterArgs `a` (its mesh is set): the checks `raster_shade` and `raycast_shade`
+  share."""
   V, T = int(a.n_verts), int(a.n_faces)
   if colors is not None and texture is not None:
     raise ValueError(f'{name}: colors and texture are both given: the colour has one source')
@@ -2013,6 +2003,22 @@ def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1.,
   if colors is not None:
     a.colors, a.colors_u8 = colors.data_ptr(), int(colors.dtype == torch.uint8)
   a.bg = (C.c_float * 3)(*finite3(name, 'bg', bg))
+
+
+def raster_shade(m, proj, vis, near, colors=None, texture=None, uv=None, bg=(1., 1., 1.)):
+  """dict(face [H,W] int32, depth [H,W], acc [H,W], bary [H,W,3], normals [H,W,3], rgb [H,W,3] float32) of a visibility buffer `vis`
+  [H,W] int64 that `raster_visibility` wrote for the same mesh, projection and near (mnr_raster_shade; include/mnerf.h): the winning
+  face (-1: none), its zc, 1 where there is one, the perspective-correct barycentrics, the interpolated unit normal and the colour:
+  `colors` [V,3] uint8 or float32 blended over the face, or `texture` [Ht,Wt,3] uint8 or float32 looked up bilinearly at the blend of
+  `uv` [T,3,2] (per face corner, v = 1 the top row: what mesh.bake_texture returns), or, with neither, 0.5 + 0.5 normal.  Pixels
+  without a face get `bg`."""
+  name = 'raster_shade'
+  _chk(vis, torch.int64, f'{name}: vis')
+  if vis.dim() != 2:
+    raise ValueError(f'{name}: vis must be [H,W], is {tuple(vis.shape)}')
+  H, W = int(vis.shape[0]), int(vis.shape[1])
+  a, keep = _raster_args(name, m, proj, H, W, near)
+  _shade_colour_args(name, a, colors, texture, uv, bg)
   dev = vis.device
   out = dict(face=torch.empty((H, W), dtype=torch.int32, device=dev), depth=torch.empty((H, W), dtype=f32, device=dev),
              acc=torch.empty((H, W), dtype=f32, device=dev), bary=torch.empty((H, W, 3), dtype=f32, device=dev),
@@ -2299,6 +2305,116 @@ def point_mesh_distance(points, verts, faces, max_dist=None, grid=None, cell=Non
   order = torch.sort((g[:, 0] * dims[1] + g[:, 1]) * dims[2] + g[:, 2]).indices.contiguous()
   L.check(lib().mnr_mesh_distance(C.byref(a), _ptr(cell_start), _ptr(pair_faces), P, _ptr(points), _ptr(order), N, lim, _ptr(d2), _ptr(face),
                                   _ptr(shells), _stream()))
+  return out
+
+
+# ----------------------------------------------------------------------------- mesh ray casting (csrc/meshray.hip)
+
+RAY_TILE = 8                       # an 8 x 8 pixel tile is one wave of mnr_mesh_raycast
+
+
+def pixel_tile_order(height, width, device):
+  """order [height width] int64 for `mesh_raycast`: the row-major pixel indices of an image, tile by tile (RAY_TILE x RAY_TILE pixels,
+  row-major inside a tile), so that a wave of 64 threads serves one tile and its lanes walk the same cells."""
+  ys, xs = torch.meshgrid(torch.arange(int(height), device=device), torch.arange(int(width), device=device), indexing='ij')
+  tiles_x = (int(width) + RAY_TILE - 1) // RAY_TILE
+  key = ((ys // RAY_TILE) * tiles_x + xs // RAY_TILE) * (RAY_TILE * RAY_TILE) + (ys % RAY_TILE) * RAY_TILE + xs % RAY_TILE
+  return torch.sort(key.reshape(-1)).indices.contiguous()
+
+
+def _grid_tensors(name, grid, T, check_faces):
+  """(cell_start, pair_faces, dims, pairs) of a `mesh_grid_build` result, checked against each other and, with check_faces, against
+  the T faces of the mesh it is used with (one max read-back)."""
+  cell_start, pair_faces, dims = grid['cell_start'], grid['pair_faces'], [int(v) for v in grid['dims']]
+  _chk(cell_start, torch.int64, f'{name}: grid cell_start')
+  _chk(pair_faces, torch.int32, f'{name}: grid pair_faces')
+  if len(dims) != 3 or min(dims) < 1 or tuple(cell_start.shape) != (dims[0] * dims[1] * dims[2] + 1,) or pair_faces.dim() != 1:
+    raise ValueError(f'{name}: grid: cell_start must be [{dims} cells + 1] and pair_faces a list')
+  P = int(pair_faces.shape[0])
+  if check_faces and P > 0 and int(pair_faces.max()) >= T:
+    raise ValueError(f'{name}: grid: pair_faces names face {int(pair_faces.max())} of a mesh of {T} faces: the grid was built for another mesh')
+  return cell_start, pair_faces, dims, P
+
+
+def mesh_raycast(origins, directions, verts, faces, t_min=0., t_max=None, cull='none', grid=None, cell=None, order=None, check_faces=True):
+  """(t [N] float32, face [N] int32, bary [N,3] float32): the nearest intersection of every ray origins[i] + t directions[i] ([N,3]
+  float32 each; the directions are NOT normalised, t is in units of their length) with the mesh (mnr_mesh_raycast; include/mnerf.h
+  states the watertight hit test, every operation in its order): the smallest t in (t_min, t_max], the lowest id among the faces that
+  attain it and the barycentrics of the hit on that face.  t_max=None: no upper limit.  cull = 'back' counts only faces whose corners
+  run counter-clockwise seen from the ray origin (the rasteriser's front).  Where nothing is hit, or the ray is not finite or has no
+  direction: t = +inf, face = -1, bary = 0.  The result is a minimum of (bits(t) << 32 | face) keys over the faces that pass a test
+  which does not know the grid: it does not depend on the grid, on `order` or on the order of the rays; two runs agree bit for bit.
+
+  `grid` is a `mesh_grid_build` result for the same verts and faces (built here when None, with `cell` as its override).  `order` [N]
+  int64 is a permutation of the rays: thread i serves ray order[i] (`pixel_tile_order` for the rays of an image); None sorts the
+  rays by the cell in which they enter the grid's box (torch), so that the lanes of a wave walk the same cells.  Face indices outside
+  the vertices raise ValueError (check_faces=False leaves them to the kernel, which skips such a face).  N = 0, no face or an empty
+  grid launches nothing."""
+  name = 'mesh_raycast'
+  _chk(origins, f32, f'{name}: origins')
+  _chk(directions, f32, f'{name}: directions')
+  if origins.dim() != 2 or origins.shape[1] != 3 or tuple(directions.shape) != tuple(origins.shape):
+    raise ValueError(f'{name}: origins and directions must be [N,3], are {tuple(origins.shape)} and {tuple(directions.shape)}')
+  V, T = _chk_mesh(name, verts, faces, check_index=check_faces)
+  t_min = C.c_float(float(t_min)).value
+  t_max = float('inf') if t_max is None else C.c_float(float(t_max)).value
+  if not (t_min >= 0. and math.isfinite(t_min)):
+    raise ValueError(f'{name}: t_min = {t_min} must be finite and not negative')
+  if not t_max > t_min:
+    raise ValueError(f'{name}: t_max = {t_max} must exceed t_min = {t_min}')
+  if cull not in L.RASTER_CULL:
+    raise ValueError(f"{name}: cull = {cull!r} must be 'none' or 'back'")
+  if grid is not None and cell is not None:
+    raise ValueError(f'{name}: grid and cell are both given')
+  N, dev = int(origins.shape[0]), origins.device
+  if order is not None:
+    _chk(order, torch.int64, f'{name}: order')
+    if tuple(order.shape) != (N,):
+      raise ValueError(f'{name}: order must be [{N}], is {tuple(order.shape)}')
+  t = torch.full((N,), float('inf'), dtype=f32, device=dev)
+  face = torch.full((N,), -1, dtype=torch.int32, device=dev)
+  bary = torch.zeros((N, 3), dtype=f32, device=dev)
+  if N == 0 or T == 0 or V == 0:
+    return t, face, bary
+  if grid is None:
+    grid = mesh_grid_build(verts, faces, cell=cell)
+  cell_start, pair_faces, dims, P = _grid_tensors(name, grid, T, check_faces)
+  if P == 0:
+    return t, face, bary
+  lo, hi = [float(v) for v in grid['origin']], [float(v) for v in grid['hi']]
+  a = _meshdist_args(verts, faces, lo, hi, C.c_float(float(grid['cell'])).value, dims)
+  if order is None:                                          # by the cell of the point where the ray enters the box (an ordering only)
+    o, h = torch.tensor(lo, dtype=f32, device=dev), torch.tensor(hi, dtype=f32, device=dev)
+    inv = 1. / directions
+    near = torch.minimum((o - origins) * inv, (h - origins) * inv)
+    enter = torch.nan_to_num(near, nan=-float('inf')).max(1).values.clamp(min=t_min, max=3e38)
+    p = torch.nan_to_num(origins + enter[:, None] * directions, nan=0., posinf=3e38, neginf=-3e38)
+    g = ((torch.minimum(torch.maximum(p, o), h) - o) / a.cell).floor()
+    g = torch.minimum(g.clamp(min=0.), torch.tensor([d - 1 for d in dims], dtype=f32, device=dev)).long()
+    order = torch.sort((g[:, 0] * dims[1] + g[:, 1]) * dims[2] + g[:, 2]).indices.contiguous()
+  L.check(lib().mnr_mesh_raycast(C.byref(a), _ptr(cell_start), _ptr(pair_faces), P, _ptr(origins), _ptr(directions), _ptr(order), N, t_min, t_max,
+                                 L.RASTER_CULL[cull], _ptr(t), _ptr(face), _ptr(bary), _stream()))
+  return t, face, bary
+
+
+def raycast_shade(m, face, bary, colors=None, texture=None, uv=None, bg=(1., 1., 1.)):
+  """dict(normals [..,3], rgb [..,3] float32) of the hits `face` [..] int32 and `bary` [..,3] float32 that `mesh_raycast` returned for
+  the mesh dict `m` (vertices, normals, faces on the device), in their leading shape (mnr_raycast_shade; include/mnerf.h): the colour
+  and normal stage of `raster_shade`, the same operations in the same order, so the same (face, bary) give the same bits.  `colors`,
+  `texture` + `uv` and `bg` are `raster_shade`'s.  Where face is -1 (or names no face): normals 0, rgb = bg."""
+  name = 'raycast_shade'
+  verts, normals, faces = m['vertices'], m['normals'], m['faces']
+  V, T = _mesh_tensors(name, verts, faces, normals, max_faces=2 ** 31 - 2)
+  _chk(face, torch.int32, f'{name}: face')
+  _chk(bary, f32, f'{name}: bary')
+  if tuple(bary.shape) != tuple(face.shape) + (3,):
+    raise ValueError(f'{name}: bary must be face\'s shape + [3], are {tuple(bary.shape)} and {tuple(face.shape)}')
+  a = L.RasterArgs()
+  a.verts, a.normals, a.faces, a.n_verts, a.n_faces = verts.data_ptr(), normals.data_ptr(), faces.data_ptr(), V, T
+  _shade_colour_args(name, a, colors, texture, uv, bg)
+  n = face.numel()
+  out = dict(normals=torch.empty_like(bary), rgb=torch.empty_like(bary))
+  L.check(lib().mnr_raycast_shade(C.byref(a), _ptr(face), _ptr(bary), n, _ptr(out['normals']), _ptr(out['rgb']), _stream()))
   return out
 
 
