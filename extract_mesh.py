@@ -11,7 +11,10 @@ are legal (the query warps like any other).  --density_threshold is scene-depend
 render.py renders it, and the depth (--tsdf_depth), opacity and colour images are fused into a truncated signed distance
 volume over the box (`mesh.tsdf_mesh`, csrc/tsdf.hip), whose zero set between observed voxels is the surface.  It has no level
 to choose; rays with opacity below --acc_threshold carve free space; colours come from the renders.  --tsdf_trunc, the
-truncation in grid spacings, is a decision: larger closes thin gaps and thickens thin structures.  Perspective cameras only.
+truncation in grid spacings, is a decision: larger closes thin gaps and thickens thin structures.  Every camera model is fused:
+an undistorted pinhole through its [3,4] matrix, lens distortion (COLMAP OPENCV), fisheye (OPENCV_FISHEYE) and the spherical
+Config.render_camtype = 'pano' through the forward camera model (`mesh.camera_record`); the run prints which.  Only an NDC ray
+space (forward_facing) is refused: the distance rendered there is not a world distance.
 
 --min_component_faces / --keep_largest drop small connected components (`mesh.filter_components`: floaters are little closed
 shells of their own) and --simplify F merges the vertices of every cube of F grid spacings into one, placed by the quadric
@@ -220,12 +223,16 @@ def main_tsdf(args, box, config, model, state, out, timed):
   from multinerf_amd import datasets
   dataset = datasets.load_dataset(args.tsdf_split, config.data_dir, config, device=model.device)
   seconds = {}
-  result, volume = mesh.tsdf_mesh(model, state.params, dataset, config, box[:3], box[3:], args.resolution, trunc_voxels=args.tsdf_trunc,
-                                  depth_key=args.tsdf_depth, acc_threshold=args.acc_threshold, frame_stride=args.tsdf_stride,
-                                  colors=not args.no_colors, timings=seconds)
+  try:
+    result, volume = mesh.tsdf_mesh(model, state.params, dataset, config, box[:3], box[3:], args.resolution, trunc_voxels=args.tsdf_trunc,
+                                    depth_key=args.tsdf_depth, acc_threshold=args.acc_threshold, frame_stride=args.tsdf_stride,
+                                    colors=not args.no_colors, timings=seconds)
+  except ValueError as e:                                  # (a camera model that cannot be fused: NDC; tsdf_mesh says why)
+    raise SystemExit(f'extract_mesh.py: --method tsdf: {e}') from None
   frames = len(range(0, dataset.size, args.tsdf_stride))
   print(f'grid {tuple(volume.shape)}, spacing {volume.spacing:.6g}, truncation {volume.trunc:.6g}, {frames} frames of '
         f'{dataset.height} x {dataset.width} ({args.tsdf_split} split, {args.tsdf_depth})')
+  print(f'projection: {volume.projection}')
   kept_faces = int(result['faces'].shape[0])
   result, t_comp, t_simp = clean_up(args, result, volume.spacing, timed)
   t_bake, t_write, t_sh = bake_and_write(args, model, result, out, timed)

@@ -195,7 +195,7 @@ int mnr_viewdir_enc_fill(int64_t B, int n, const float* viewdirs, int deg_view,
  * pixtocam_ndc: device [3,3] or NULL (NDC rays, camera_utils.py:32-98).
  * Outputs fp32 device: origins, directions, viewdirs [B,3], radii [B], imageplane [B,2].
  * ------------------------------------------------------------------------- */
-typedef enum { MNR_CAM_PERSPECTIVE = 0, MNR_CAM_FISHEYE = 1 } mnr_camtype;
+typedef enum { MNR_CAM_PERSPECTIVE = 0, MNR_CAM_FISHEYE = 1, MNR_CAM_PANO = 2 /* camera records only, see below */ } mnr_camtype;
 int mnr_pixels_to_rays(int64_t B, const int32_t* pix_x_int, const int32_t* pix_y_int, const int32_t* cam_idx,
                        int num_cams, const float* pixtocams, const float* camtoworlds, const float* distortion6,
                        const float* pixtocam_ndc, int camtype, float* origins, float* directions, float* viewdirs,
@@ -208,6 +208,53 @@ int mnr_pixels_to_rays(int64_t B, const int32_t* pix_x_int, const int32_t* pix_y
  * [H,W,3] (viewdirs = directions: unit already), radii [H,W], imageplane [H,W,2] = 0. */
 int mnr_spherical_rays(int H, int W, const float* camtoworld, float* origins, float* directions, float* viewdirs,
                        float* radii, float* imageplane, void* stream);
+
+/* ------------------------------------------------------------------------- *
+ * The forward camera model: world point -> pixel  (csrc/camera_project.h; mnr_project_points in csrc/camera.hip,
+ * mnr_tsdf_integrate_cam in csrc/tsdf.hip)
+ * The inverse of the two ray generators above, for the rays in WORLD space (no NDC): a point X = origins + s directions of pixel
+ * (px, py) maps to (u, v) with int(u) = px, int(v) = py, and to that s.  s is the ray parameter in units of the length of
+ * `directions`, i.e. the distance a model renders along those rays: the camera-space depth for a perspective camera (the ray's
+ * camera-space z is 1), the Euclidean distance for fisheye and pano (unit directions).
+ *
+ * A camera is a RECORD of MNR_CAM_REC = 28 floats (mesh.camera_record builds it in float64 and rounds once):
+ *   [0..11]   M [3,4] = diag(1,-1,-1) [R^T | -R^T o] for camtoworld = [R | o]: world -> OpenCV camera frame
+ *   [12..17]  a [2,3]: the first two rows of inv(pixtocam); the last row of pixtocam must be (0, 0, 1)
+ *   [18..23]  k1, k2, k3, k4, p1, p2 (all 0: no lens distortion)
+ *   [24]      r2_max, the fold-back guard (below)      [25] the model, an mnr_camtype as a float
+ *   [26]      float(H)                                 [27] float(W)
+ * For MNR_CAM_PANO only M, the model, H and W are read.
+ *
+ * Per point (x, y, z), float32 in the order written, no contraction; a comparison with a NaN is false, so ok is false:
+ *   c_r = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3] for r = 0, 1, 2.
+ *   PERSPECTIVE  ok = c_2 > 0;  X = c_0 / c_2, Y = c_1 / c_2, s = c_2;  r = X X + Y Y;  ok = ok and r <= r2_max.
+ *   FISHEYE      h = sqrtf(c_0 c_0 + c_1 c_1), theta = atan2f(h, c_2), q = theta / h (0 where h == 0), X = q c_0, Y = q c_1,
+ *                s = sqrtf((c_0 c_0 + c_1 c_1) + c_2 c_2);  r = X X + Y Y;  ok = theta theta <= r2_max and (h > 0 or c_2 > 0)
+ *                (h == 0 and c_2 <= 0 is the eye itself or the one direction every pixel at theta = pi shares).
+ *   both         d = 1 + r (k1 + r (k2 + r (k3 + r k4)));
+ *                xd = (d X + ((2 p1) X) Y) + p2 (r + (2 X) X),  yd = (d Y + ((2 p2) X) Y) + p1 (r + (2 Y) Y)
+ *                (cam_undistort's fx, fy without the "- xd", "- yd");
+ *                u = (a00 xd + a01 yd) + a02,  v = (a10 xd + a11 yd) + a12.
+ *   PANO         s = sqrtf((c_0 c_0 + c_1 c_1) + c_2 c_2);  ok = 0 < s < inf;  n_y = min(1, max(-1, -c_1 / s));
+ *                phi = acosf(n_y);  theta = atan2f(-c_0, -c_2), + 6.2831855f where negative;
+ *                u = theta W / 6.2831855f + 0.5f, - W where u >= W;  v = phi H / 3.1415927f + 0.5f, H - 0.5f where v >= H
+ *                (mnr_spherical_rays' pixel (h, w) looks along theta = 2 pi w / W, phi = pi h / H: a grid POINT, so int(u), int(v)
+ *                are the nearest grid point, column W wrapping to 0 and row H, the pole, going to row H - 1).
+ *   valid = ok and 0 <= u < W and 0 <= v < H.  Pixel px covers [px, px + 1).
+ * The perspective model uses only + - x / and comparisons: a NumPy float32 restatement reproduces it bit for bit.
+ *
+ * The fold-back guard.  The distortion polynomial is not injective: far outside the image it folds back, and a point there would
+ * land inside the image, mirrored.  r2_max bounds X X + Y Y (for fisheye theta theta) to the image's own pre-image: the host
+ * undistorts the pixel corners along the four image edges (Newton, float64, to convergence), takes the largest squared radius,
+ * times 1.01^2 for the border between the corners, at most pi^2 for fisheye.  The radius' maximum over the pre-image lies on its
+ * border, so the guard drops nothing that is in the image.
+ *
+ * mnr_project_points: points [n,3] (device) through ONE record (28 floats, a HOST pointer, copied at the call) ->
+ * uv [n,2], s [n] float32 and valid [n] bytes (device); one thread a point.  u, v and s are written whatever valid is.
+ * n == 0 is a successful no-op.
+ * ------------------------------------------------------------------------- */
+#define MNR_CAM_REC 28
+int mnr_project_points(int64_t n, const float* points, const float* record, float* uv, float* s, unsigned char* valid, void* stream);
 
 /* GLO vectors (models.py:101-110,565-568): dst[b*n+i, col0+g] = table[cam_idx[b], g] (bf16), or 0 when
  * cam_idx is NULL (zero_glo=True).  table [num_embeddings, G] fp32 = params['Embed_0']['embedding']. */
@@ -965,6 +1012,34 @@ typedef struct {
   float* color;                    /* [nx,ny,nz,3] or NULL (rgb and color: both or neither), updated in place */
 } mnr_tsdf_args;
 int mnr_tsdf_integrate(const mnr_tsdf_args* args, void* stream);
+
+/* The same fusion for any camera model: cameras [F,MNR_CAM_REC] (device) holds one record a frame (the forward camera model
+ * above), all of the model `model` and of the images' H and W; depth holds s, the distance rendered along the camera's own rays.
+ * The seven steps stay, with steps 2 and 3 replaced by the forward model:
+ *   2/3. (u, v, s, ok) of the frame's record at (x, y, z); skip the frame unless ok and 0 <= u < float(W) and 0 <= v < float(H);
+ *        px = int(u), py = int(v);
+ *   5.   ... skip unless 0 < d < inf; e = d - s; skip if e < -trunc; t = min(1, e / trunc).
+ * A record whose model, H or W is not the call's is skipped as a whole.  Everything else (frames in ascending order, the sums
+ * folded after the last frame of a launch, MNR_TSDF_MAX_FRAMES frames a launch, no atomics) is as stated above.  For
+ * MNR_CAM_PERSPECTIVE a NumPy float32 restatement reproduces the volumes bit for bit; fisheye and pano call atan2f and acosf.
+ * mnr_tsdf_integrate itself is untouched: an undistorted pinhole keeps its [3,4] matrix and its kernel. */
+typedef struct {
+  int nx, ny, nz;
+  float origin[3];
+  float spacing;                   /* > 0, finite */
+  float trunc;                     /* world units, > 0, finite */
+  int F, H, W;
+  int model;                       /* mnr_camtype of every record */
+  const float* cameras;            /* [F,MNR_CAM_REC] */
+  const float* depth;              /* [F,H,W] */
+  const float* acc;                /* [F,H,W] or NULL */
+  float acc_threshold;
+  const float* rgb;                /* [F,H,W,3] or NULL */
+  float* tsdf;                     /* [nx,ny,nz], updated in place */
+  float* weight;                   /* [nx,ny,nz], updated in place */
+  float* color;                    /* [nx,ny,nz,3] or NULL (rgb and color: both or neither), updated in place */
+} mnr_tsdf_cam_args;
+int mnr_tsdf_integrate_cam(const mnr_tsdf_cam_args* args, void* stream);
 
 /* keep[id] = 1 iff both ends of vertex id's grid edge have valid != 0, else 0, for the vertices of a mesh the three passes above
  * produced: args carries that run's nx, ny, nz, mask, base and n_verts; valid [points] and keep [n_verts] are bytes.  As in the

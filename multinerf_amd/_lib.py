@@ -218,6 +218,16 @@ class TsdfArgs(C.Structure):
               ('rgb', vp), ('tsdf', vp), ('weight', vp), ('color', vp)]
 
 
+CAM_REC = 28                       # MNR_CAM_REC: floats of a camera record (include/mnerf.h, "The forward camera model")
+CAM_MODEL = {'perspective': 0, 'fisheye': 1, 'pano': 2}      # mnr_camtype
+
+
+class TsdfCamArgs(C.Structure):
+  _fields_ = [('nx', C.c_int), ('ny', C.c_int), ('nz', C.c_int), ('origin', C.c_float * 3), ('spacing', C.c_float), ('trunc', C.c_float),
+              ('F', C.c_int), ('H', C.c_int), ('W', C.c_int), ('model', C.c_int), ('cameras', vp), ('depth', vp), ('acc', vp),
+              ('acc_threshold', C.c_float), ('rgb', vp), ('tsdf', vp), ('weight', vp), ('color', vp)]
+
+
 QEM_REG = 1e-3                     # MNR_QEM_REG
 MESH_CELL_LIMIT = 1 << 21          # MNR_MESH_CELL_LIMIT
 MESH_KEY_NONFINITE, MESH_KEY_OUTSIDE = -1, -2
@@ -364,6 +374,8 @@ _PROTOS = {
     'mnr_mt_emit_vertices': ([C.POINTER(MtArgs), vp], i32),
     'mnr_mt_emit_faces': ([C.POINTER(MtArgs), vp], i32),
     'mnr_tsdf_integrate': ([C.POINTER(TsdfArgs), vp], i32),
+    'mnr_tsdf_integrate_cam': ([C.POINTER(TsdfCamArgs), vp], i32),
+    'mnr_project_points': ([i64, vp, C.POINTER(C.c_float), vp, vp, vp, vp], i32),
     'mnr_mt_vertex_valid': ([C.POINTER(MtArgs), vp, vp, vp], i32),
     'mnr_mesh_cc_init': ([i64, vp, vp], i32),
     'mnr_mesh_cc_sweep': ([vp, i64, i64, vp, vp, vp], i32),

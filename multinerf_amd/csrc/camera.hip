@@ -6,6 +6,7 @@
 // fp32 throughout, FP contraction off so that the arithmetic follows the reference's operation order.
 
 #include "common.h"
+#include "camera_project.h"                                 // the forward model: mnr_project_points at the end of this file
 
 #pragma clang fp contract(off)
 
@@ -216,6 +217,49 @@ extern "C" int mnr_spherical_rays(int H, int W, const float* camtoworld, float* 
   MNR_CHECK_ARG(camtoworld && origins && directions && viewdirs && radii && imageplane, "mnr_spherical_rays: null argument");
   hipLaunchKernelGGL(spherical_rays_kernel, dim3(mnr_cdiv((int64_t)H * W, 256)), dim3(256), 0, (hipStream_t)stream, H, W, camtoworld,
                      origins, directions, viewdirs, radii, imageplane);
+  MNR_CHECK_LAUNCH();
+  return MNR_OK;
+}
+
+// ---- world point -> pixel (camera_project.h; include/mnerf.h states every operation).  One thread a point, one record a call:
+// the record travels as a kernel argument, so every lane reads it from scalar registers.
+struct CamRecord {
+  float v[MNR_CAM_REC];
+};
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void project_points_kernel(int64_t n, const float* __restrict__ points, CamRecord rec, float* __restrict__ uv,
+                                                            float* __restrict__ s_out, unsigned char* __restrict__ valid) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= n) return;
+  const float Hf = rec.v[CAMP_H], Wf = rec.v[CAMP_W];
+  float u, v, s;
+  const bool ok = cam_project<MODEL>(rec.v, Hf, Wf, points[b * 3 + 0], points[b * 3 + 1], points[b * 3 + 2], u, v, s);
+  uv[b * 2 + 0] = u;
+  uv[b * 2 + 1] = v;
+  s_out[b] = s;
+  valid[b] = (ok && cam_on_image(u, v, Hf, Wf)) ? 1 : 0;
+}
+
+extern "C" int mnr_project_points(int64_t n, const float* points, const float* record, float* uv, float* s, unsigned char* valid, void* stream) {
+  MNR_CHECK_ARG(n >= 0 && n < (1ll << 31), "mnr_project_points: n = %lld points: must lie in 0 .. 2^31 - 1", (long long)n);
+  MNR_CHECK_ARG(record, "mnr_project_points: needs the camera record (%d floats, a host pointer)", MNR_CAM_REC);
+  CamRecord rec;
+  for (int i = 0; i < MNR_CAM_REC; ++i) rec.v[i] = record[i];
+  const float model = rec.v[CAMP_MODEL];
+  MNR_CHECK_ARG(model == (float)MNR_CAM_PERSPECTIVE || model == (float)MNR_CAM_FISHEYE || model == (float)MNR_CAM_PANO,
+                "mnr_project_points: the record's model is %g: must be 0 (perspective), 1 (fisheye) or 2 (pano)", (double)model);
+  MNR_CHECK_ARG(rec.v[CAMP_H] >= 1.f && rec.v[CAMP_W] >= 1.f && rec.v[CAMP_H] <= 16777216.f && rec.v[CAMP_W] <= 16777216.f,
+                "mnr_project_points: the record's image is [%g, %g]: both sides must lie in 1 .. 2^24", (double)rec.v[CAMP_H], (double)rec.v[CAMP_W]);
+  if (n == 0) return MNR_OK;
+  MNR_CHECK_ARG(points && uv && s && valid, "mnr_project_points: needs points [n,3], uv [n,2], s [n] and valid [n]");
+  const dim3 grid(mnr_cdiv(n, 256)), block(256);
+  if (model == (float)MNR_CAM_PANO)
+    hipLaunchKernelGGL(project_points_kernel<MNR_CAM_PANO>, grid, block, 0, (hipStream_t)stream, n, points, rec, uv, s, valid);
+  else if (model == (float)MNR_CAM_FISHEYE)
+    hipLaunchKernelGGL(project_points_kernel<MNR_CAM_FISHEYE>, grid, block, 0, (hipStream_t)stream, n, points, rec, uv, s, valid);
+  else
+    hipLaunchKernelGGL(project_points_kernel<MNR_CAM_PERSPECTIVE>, grid, block, 0, (hipStream_t)stream, n, points, rec, uv, s, valid);
   MNR_CHECK_LAUNCH();
   return MNR_OK;
 }

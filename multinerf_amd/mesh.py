@@ -3,6 +3,8 @@
   density_grid   the field of a density function on a box, queried chunk by chunk on the device
   extract_mesh   density_grid of `model.query_density`, ops.marching_tetrahedra (csrc/mesh.hip), colours from `model.nerf_hp`
   world_to_pixel the [3,4] projection of a perspective camera that csrc/tsdf.hip reads
+  camera_record / project_points   any camera model the other way round, world point -> pixel: the packed record of the forward
+                 model with its fold-back guard, and points through it on the device (csrc/camera_project.h)
   TsdfVolume     a truncated signed distance volume: integrate depth images (ops.tsdf_integrate, csrc/tsdf.hip), mesh its zero set
   tsdf_mesh      render the cameras of a dataset and fuse their depth into a TsdfVolume
   write_ply / read_ply   binary_little_endian 1.0
@@ -167,6 +169,143 @@ def camera_is_pinhole(distortion_params=None, pixtocam_ndc=None, camtype=camera_
   return camera_utils.ProjectionType(camtype) == camera_utils.ProjectionType.PERSPECTIVE
 
 
+_DISTORTION_KEYS = ('k1', 'k2', 'k3', 'k4', 'p1', 'p2')
+
+
+def _distortion(x, y, k):
+  """The lens distortion of camera_utils and its Jacobian, float64: (xd, yd, dxd/dx, dxd/dy, dyd/dx, dyd/dy), the terms of the
+  undistortion's residual and Jacobian (csrc/camera.hip's cam_undistort) without the target."""
+  r = x * x + y * y
+  d = 1. + r * (k[0] + r * (k[1] + r * (k[2] + r * k[3])))
+  d_r = k[0] + r * (2. * k[1] + r * (3. * k[2] + r * 4. * k[3]))
+  d_x, d_y = 2. * x * d_r, 2. * y * d_r
+  return (d * x + 2. * k[4] * x * y + k[5] * (r + 2. * x * x), d * y + 2. * k[5] * x * y + k[4] * (r + 2. * y * y),
+          d + d_x * x + 2. * k[4] * y + 6. * k[5] * x, d_y * x + 2. * k[4] * x + 2. * k[5] * y,
+          d_x * y + 2. * k[5] * y + 2. * k[4] * x, d + d_y * y + 2. * k[5] * x + 6. * k[4] * y)
+
+
+def _distort(x, y, k):
+  return _distortion(x, y, k)[:2]
+
+
+def _undistort(xd, yd, k, eps=1e-9, max_iterations=200):
+  """camera_utils' Newton iteration from the distorted point (csrc/camera.hip's cam_undistort), in float64 and run until no
+  coordinate moves by more than 1e-15 (or max_iterations)."""
+  x, y = xd.copy(), yd.copy()
+  for _ in range(max_iterations):
+    bx, by, fx_x, fx_y, fy_x, fy_y = _distortion(x, y, k)
+    fx, fy = bx - xd, by - yd
+    den = fy_x * fx_y - fx_x * fy_y
+    ok = np.abs(den) > eps
+    safe = np.where(ok, den, 1.)
+    sx, sy = np.where(ok, (fx * fy_y - fy * fx_y) / safe, 0.), np.where(ok, (fy * fx_x - fx * fy_x) / safe, 0.)
+    x, y = x + sx, y + sy
+    if max(np.abs(sx).max(), np.abs(sy).max()) <= 1e-15:
+      break
+  return x, y
+
+
+def fold_back_guard(pixtocam, height, width, k, fisheye=False):
+  """r2_max of a camera record: the largest squared radius x^2 + y^2 of the UNDISTORTED image-plane points that the image's border
+  comes from, times 1.01^2, at most pi^2 for a fisheye camera (where the radius is the angle theta); float64 on the host.
+
+  The distortion polynomial is not injective: beyond the image it folds back, and a point out there would project into the image,
+  mirrored.  The forward model (include/mnerf.h) therefore accepts a point only with x^2 + y^2 <= r2_max.  The border is sampled at
+  the pixel corners along the four image edges (1.01 covers the sampling between them), sent through pixtocam and undistorted
+  with the ray model's own Newton iteration, run to convergence.  The radius has no interior maximum over the image's pre-image,
+  so the guard drops nothing that is in the image.  Every sample, distorted forward again, must come back to within 1e-3 pixel
+  (a converged one does to 1e-12, a failed one is off by pixels), and it must lie on the branch of the distortion that contains
+  the optical axis: the distortion's Jacobian there has a positive determinant and a positive trace, as it has at the centre,
+  where it is the identity.  (Past the fold the iteration can converge too, to the MIRRORED root on the far side of the axis,
+  which distorts forward exactly but has a reflected Jacobian.)  Otherwise the image reaches past the region where the model can
+  be inverted, and this raises ValueError."""
+  P = _host(pixtocam, np.float64).reshape(3, 3)
+  H, W = int(height), int(width)
+  us, vs = np.arange(W + 1, dtype=np.float64), np.arange(H + 1, dtype=np.float64)
+  u = np.concatenate([us, us, np.zeros_like(vs), np.full_like(vs, W)])
+  v = np.concatenate([np.zeros_like(us), np.full_like(us, H), vs, vs])
+  xd, yd = P[0, 0] * u + P[0, 1] * v + P[0, 2], P[1, 0] * u + P[1, 1] * v + P[1, 2]
+  k = [float(c) for c in k]
+  with np.errstate(all='ignore'):
+    x, y = _undistort(xd, yd, k)
+    bx, by, j00, j01, j10, j11 = _distortion(x, y, k)
+    A = np.linalg.inv(P)
+    du, dv = A[0, 0] * bx + A[0, 1] * by + A[0, 2] - u, A[1, 0] * bx + A[1, 1] * by + A[1, 2] - v
+    err = np.max(np.hypot(du, dv))
+    principal = bool(((j00 * j11 - j01 * j10 > 0.) & (j00 + j11 > 0.)).all())
+  if err <= 1e-3 and not principal:
+    raise ValueError(f'fold_back_guard: a point on the border of the {H} x {W} image undistorts to the mirrored branch of the distortion '
+                     'model: the image reaches past the region where the distortion model can be inverted')
+  if not (err <= 1e-3):
+    raise ValueError(f'fold_back_guard: a point on the border of the {H} x {W} image comes back {err:.3g} pixels from where it started after '
+                     'undistortion and distortion: the image reaches past the region where the distortion model can be inverted')
+  r2 = float(np.max(x * x + y * y)) * 1.01 ** 2
+  return min(r2, math.pi ** 2) if fisheye else r2
+
+
+def camera_record(pixtocam, camtoworld, height, width, distortion_params=None, pixtocam_ndc=None,
+                  camtype=camera_utils.ProjectionType.PERSPECTIVE):
+  """The packed float32 record [_lib.CAM_REC] (a host array) of the FORWARD camera model, world point -> pixel, for
+  ops.project_points and ops.tsdf_integrate_cam; include/mnerf.h states the layout and every operation: the world-to-camera rows
+  diag(1,-1,-1) [R^T | -R^T o] of camtoworld = [R | o] (12), the first two rows of inv(pixtocam) (6), k1 .. k4, p1, p2 (6),
+  `fold_back_guard` (1), the model, height, width.  Computed in float64, rounded once.
+
+  It inverts the project's own rays: camera_utils.pixels_to_rays for a perspective or fisheye `camtype` with or without
+  `distortion_params`, ops.spherical_rays for camtype = 'pano' (pixtocam and distortion_params are then not read).  Refused with a
+  ValueError: an NDC ray space (pixtocam_ndc: the distance a model renders there is not a world distance, so there is nothing a
+  world point's depth could be compared with), a pixtocam whose last row is not exactly (0, 0, 1) (the distorted ray model sets
+  the ray's camera-space z to 1, i.e. assumes that row), a camtoworld whose R is not a rotation to 1e-4, and an image that reaches
+  past the distortion model's invertible region (`fold_back_guard`)."""
+  if pixtocam_ndc is not None:
+    raise ValueError('camera_record: pixtocam_ndc is given: rays in NDC space are refused, the distance a model renders along them is '
+                     'not a world distance')
+  pano = isinstance(camtype, str) and camtype == 'pano'
+  H, W = int(height), int(width)
+  if not (1 <= H <= 1 << 24 and 1 <= W <= 1 << 24):
+    raise ValueError(f'camera_record: an image of [{H}, {W}]: both sides must lie in 1 .. 2^24')
+  c2w = _host(camtoworld, np.float64)[..., :3, :4].reshape(3, 4)
+  R, o = c2w[:, :3], c2w[:, 3]
+  if not np.isfinite(c2w).all() or np.abs(R.T @ R - np.eye(3)).max() > 1e-4:
+    raise ValueError('camera_record: the left 3 x 3 block of camtoworld must be a rotation (R^T R = 1 to 1e-4)')
+  rec = np.zeros((L.CAM_REC,), np.float64)
+  rec[0:12] = (np.diag([1., -1., -1.]) @ np.concatenate([R.T, -(R.T @ o)[:, None]], 1)).reshape(-1)
+  rec[26], rec[27] = H, W
+  if pano:
+    rec[25] = L.CAM_MODEL['pano']
+    return rec.astype(np.float32)
+  fisheye = camera_utils.ProjectionType(camtype) == camera_utils.ProjectionType.FISHEYE
+  P = _host(pixtocam, np.float64).reshape(3, 3)
+  if not np.array_equal(P[2], [0., 0., 1.]):
+    raise ValueError(f'camera_record: the last row of pixtocam is {P[2].tolist()}, not (0, 0, 1): the distorted ray model assumes that row')
+  if not np.isfinite(P).all() or np.linalg.matrix_rank(P) < 3:
+    raise ValueError('camera_record: pixtocam is singular or not finite')
+  distortion_params = dict(distortion_params or {})
+  unknown = sorted(set(distortion_params) - set(_DISTORTION_KEYS))
+  if unknown:
+    raise ValueError(f'camera_record: distortion_params has unknown keys {unknown}; known: {list(_DISTORTION_KEYS)}')
+  k = [float(distortion_params.get(name, 0.)) for name in _DISTORTION_KEYS]
+  rec[12:18] = np.linalg.inv(P)[:2].reshape(-1)
+  rec[18:24] = k
+  rec[24] = fold_back_guard(P, H, W, k, fisheye=fisheye)
+  rec[25] = L.CAM_MODEL['fisheye' if fisheye else 'perspective']
+  return rec.astype(np.float32)
+
+
+def project_points(points, pixtocam, camtoworld, height, width, distortion_params=None, camtype=camera_utils.ProjectionType.PERSPECTIVE):
+  """World points seen by any camera model: (uv [..,2] float32, s [..] float32, valid [..] bool) of `points` [..,3] (a device tensor,
+  or a host array that is moved to 'cuda'), on the device (ops.project_points, csrc/camera.hip, through `camera_record`).  It is the
+  inverse of the project's ray generators: origins + s directions of pixel (px, py) gives int(u) = px, int(v) = py and that s, the
+  distance a model renders along the ray and the depth of render_mesh(method='raycast').  valid: in front of the camera model,
+  inside the fold-back guard and on the image (pixel px covers [px, px + 1)); a 'pano' camera sees every point but its own eye."""
+  rec = camera_record(pixtocam, camtoworld, height, width, distortion_params=distortion_params, camtype=camtype)
+  p = points.to(torch.float32) if torch.is_tensor(points) else torch.as_tensor(np.asarray(points, np.float32)).to('cuda')
+  if p.dim() < 1 or p.shape[-1] != 3:
+    raise ValueError(f'project_points: points must be [..,3], are {tuple(p.shape)}')
+  lead = tuple(p.shape[:-1])
+  uv, s, valid = ops.project_points(p.reshape(-1, 3).contiguous(), rec)
+  return uv.reshape(lead + (2,)), s.reshape(lead), valid.reshape(lead)
+
+
 # the 7 edge directions of csrc/mesh.hip, by edge number
 _EDGE_DIRS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
 
@@ -187,22 +326,35 @@ class TsdfVolume:
     self.tsdf = torch.ones(self.shape, dtype=torch.float32, device=device)
     self.weight = torch.zeros(self.shape, dtype=torch.float32, device=device)
     self.color = torch.zeros(self.shape + (3,), dtype=torch.float32, device=device) if colors else None
+    self.projection = None                                  # set by tsdf_mesh: which projection its frames went through
 
-  def integrate(self, depth, proj, acc=None, rgb=None, acc_threshold=0.5):
+  def integrate(self, depth, proj=None, acc=None, rgb=None, acc_threshold=0.5, cameras=None):
     """Fuse one frame (depth [H,W], proj [3,4]) or a stack ([F,H,W], [F,3,4]): depth is zc along the rays of `world_to_pixel`'s
     camera (0, negative, infinite or NaN: no measurement), acc (optional) the rays' opacity, below `acc_threshold` an empty ray
-    that marks what it crosses as free space, rgb [...,3] the colours (required with a colour volume, ignored without)."""
+    that marks what it crosses as free space, rgb [...,3] the colours (required with a colour volume, ignored without).
+
+    cameras= takes the place of proj for a camera that has no [3,4] matrix: one `camera_record` ([_lib.CAM_REC]) or a stack of them,
+    all of one model (ops.tsdf_integrate_cam); depth is then the distance along the camera's own rays, what a model renders and
+    what render_mesh(method='raycast') returns.  Exactly one of proj and cameras is given."""
+    if (proj is None) == (cameras is None):
+      raise ValueError('TsdfVolume.integrate: exactly one of proj (a pinhole [3,4] matrix a frame) and cameras (a camera record a frame) is given')
     dev = self.tsdf.device
     to = lambda x: None if x is None else torch.as_tensor(x).to(device=dev, dtype=torch.float32)
     depth, proj, acc, rgb = to(depth), to(proj), to(acc), to(rgb)
+    if cameras is not None:
+      cameras = np.asarray(cameras.detach().cpu().numpy() if torch.is_tensor(cameras) else cameras, np.float32)
     if depth.dim() == 2:
-      depth, proj = depth[None], proj[None]
+      depth, proj, cameras = depth[None], (None if proj is None else proj[None]), (None if cameras is None else cameras[None])
       acc, rgb = (None if acc is None else acc[None]), (None if rgb is None else rgb[None])
     if self.color is None:
       rgb = None
     elif rgb is None:
       raise ValueError('TsdfVolume.integrate: a volume with colours needs rgb')
     c = lambda x: None if x is None else x.contiguous()
+    if cameras is not None:
+      ops.tsdf_integrate_cam(self.tsdf, self.weight, self.color, self.origin, self.spacing, self.trunc, cameras, c(depth), acc=c(acc),
+                             rgb=c(rgb), acc_threshold=acc_threshold)
+      return
     ops.tsdf_integrate(self.tsdf, self.weight, self.color, self.origin, self.spacing, self.trunc, c(proj), c(depth), acc=c(acc),
                        rgb=c(rgb), acc_threshold=acc_threshold)
 
@@ -242,9 +394,15 @@ def tsdf_mesh(model, params, dataset, config, bbox_min, bbox_max, resolution, tr
   The frames are rendered the way render.py renders them (train_utils.create_render_fn, models.render_image, rng=None) with
   the bound parameters `params` (the `variables` of construct_model / a restored state's params); `depth_key`
   ('distance_median' or 'distance_mean'), 'acc' and 'rgb' of `frames_per_call` frames are stacked and integrated in one call.
-  The cameras must be undistorted perspective cameras (`world_to_pixel` refuses the others).  A dict passed as `timings` gets the
-  seconds of 'render', 'fusion' and 'isosurface' (each bracketed by a device synchronisation)."""
+  Any camera model but an NDC ray space is fused: an undistorted pinhole (`camera_is_pinhole`) goes through `world_to_pixel` and
+  the [3,4] kernel exactly as before; lens distortion, a fisheye lens and the spherical 'pano' render camera go through
+  `camera_record` and ops.tsdf_integrate_cam, the rendered distance being the ray parameter either way.  The volume's `projection`
+  says which ('pinhole matrix' or 'camera records (<model>)').  A dict passed as `timings` gets the seconds of 'render', 'fusion'
+  and 'isosurface' (each bracketed by a device synchronisation)."""
   from multinerf_amd import train_utils
+  if dataset.pixtocam_ndc is not None:                      # (the one place that says so: extract_mesh.py passes this message on)
+    raise ValueError('tsdf_mesh: the dataset renders in an NDC ray space (forward_facing): the rendered distance is not a world distance, '
+                     'so it cannot be fused into a world-space volume')
   if depth_key not in ('distance_median', 'distance_mean'):
     raise ValueError(f"tsdf_mesh: depth_key = {depth_key!r} must be 'distance_median' or 'distance_mean'")
   frame_stride, frames_per_call = int(frame_stride), int(frames_per_call)
@@ -252,7 +410,9 @@ def tsdf_mesh(model, params, dataset, config, bbox_min, bbox_max, resolution, tr
     raise ValueError('tsdf_mesh: frame_stride and frames_per_call must be positive')
   camtype = 'pano' if getattr(dataset, '_render_spherical', False) else dataset.camtype
   pixtocams = _host(dataset.pixtocams, np.float64)
+  pinhole = camera_is_pinhole(dataset.distortion_params, None, camtype)
   volume = TsdfVolume(bbox_min, bbox_max, resolution, trunc_voxels=trunc_voxels, colors=colors, device=model.device)
+  volume.projection = 'pinhole matrix' if pinhole else f'camera records ({camtype if isinstance(camtype, str) else camtype.value})'
   render_fn = train_utils.create_render_fn(model)
   seconds = dict(render=0., fusion=0., isosurface=0.)
 
@@ -268,18 +428,24 @@ def tsdf_mesh(model, params, dataset, config, bbox_min, bbox_max, resolution, tr
 
   def flush(stack):
     if stack:
-      depth, proj, acc, rgb = (torch.stack([s[n] for s in stack], 0) for n in range(4))
-      timed('fusion', lambda: volume.integrate(depth, proj, acc=acc, rgb=rgb if colors else None, acc_threshold=acc_threshold))
+      depth, proj, acc, rgb = ((torch if torch.is_tensor(stack[0][n]) else np).stack([s[n] for s in stack], 0) for n in range(4))
+      kw = dict(proj=proj) if pinhole else dict(cameras=proj)
+      timed('fusion', lambda: volume.integrate(depth, acc=acc, rgb=rgb if colors else None, acc_threshold=acc_threshold, **kw))
     del stack[:]
 
   stack = []
   for idx in range(0, dataset.size, frame_stride):
-    proj = world_to_pixel(pixtocams if pixtocams.ndim == 2 else pixtocams[idx], dataset.camtoworlds[idx],
-                          distortion_params=dataset.distortion_params, pixtocam_ndc=dataset.pixtocam_ndc, camtype=camtype)
+    pixtocam = pixtocams if pixtocams.ndim == 2 else pixtocams[idx]
+    if pinhole:
+      proj = torch.as_tensor(world_to_pixel(pixtocam, dataset.camtoworlds[idx], distortion_params=dataset.distortion_params,
+                                            pixtocam_ndc=dataset.pixtocam_ndc, camtype=camtype)).to(model.device)
+    else:                                                   # (a host record: ops.tsdf_integrate_cam checks and uploads the stack)
+      proj = camera_record(pixtocam, dataset.camtoworlds[idx], dataset.height, dataset.width, distortion_params=dataset.distortion_params,
+                           camtype=camtype)
     rays = dataset.generate_ray_batch(idx).rays
     r = timed('render', lambda: models.render_image(lambda rng, chunk: render_fn(params, 1.0, None, chunk), rays, None, config,
                                                     verbose=False))
-    stack.append((r[depth_key].to(torch.float32), torch.as_tensor(proj).to(model.device), r['acc'].to(torch.float32),
+    stack.append((r[depth_key].to(torch.float32), proj, r['acc'].to(torch.float32),
                   r['rgb'].to(torch.float32)))
     if len(stack) == frames_per_call:
       flush(stack)

@@ -9,6 +9,7 @@ import ctypes as C
 import math
 import os
 
+import numpy as np
 import torch
 
 from multinerf_amd import _lib as L
@@ -1211,6 +1212,38 @@ def spherical_rays(camtoworld, height, width):
   return origins, directions, viewdirs, radii, imageplane
 
 
+def camera_record_host(name, record, rows=None):
+  """A camera record, or a stack of `rows` of them, as a contiguous float32 host array [.., _lib.CAM_REC] (include/mnerf.h, "The
+  forward camera model"; mesh.camera_record builds them), and the one model all of them name.  ValueError for another length,
+  values that are not finite, a model that is none of _lib.CAM_MODEL, or models that differ."""
+  rec = record.detach().cpu().numpy() if torch.is_tensor(record) else record
+  rec = np.ascontiguousarray(rec, dtype=np.float32)
+  want = (L.CAM_REC,) if rows is None else (rows, L.CAM_REC)
+  if rec.shape != want:
+    raise ValueError(f'{name}: the camera record(s) must be {list(want)} float32 (mesh.camera_record), are {list(rec.shape)}')
+  if not np.isfinite(rec).all():
+    raise ValueError(f'{name}: a camera record holds a value that is not finite')
+  models = np.unique(rec.reshape(-1, L.CAM_REC)[:, 25])
+  if len(models) > 1 or (len(models) == 1 and float(models[0]) not in (0., 1., 2.)):
+    raise ValueError(f'{name}: the records must all name one camera model of {L.CAM_MODEL}, theirs are {models.tolist()}')
+  return rec, (int(models[0]) if len(models) else 0)
+
+
+def project_points(points, record):
+  """World points through one camera (mnr_project_points; include/mnerf.h states every operation of the forward model): points
+  [n,3] float32 on the device, `record` the _lib.CAM_REC floats of mesh.camera_record (a host array or any tensor) ->
+  (uv [n,2] float32, s [n] float32, valid [n] bool).  s is the ray parameter of the point along its pixel's `directions`
+  (camera_utils.pixels_to_rays, ops.spherical_rays); valid = in front of the model, inside the fold-back guard and on the image,
+  and int(u), int(v) is then the pixel."""
+  n = _chk_points('project_points', 'points', points)
+  rec, _ = camera_record_host('project_points', record)
+  uv = torch.empty((n, 2), dtype=f32, device=points.device)
+  s = torch.empty((n,), dtype=f32, device=points.device)
+  valid = torch.empty((n,), dtype=torch.uint8, device=points.device)
+  L.check(lib().mnr_project_points(n, _ptr(points), rec.ctypes.data_as(C.POINTER(C.c_float)), _ptr(uv), _ptr(s), _ptr(valid), _stream()))
+  return uv, s, valid.bool()
+
+
 def weighted_percentile(x, w, ps, assume_sorted=False, out=None):
   """vis.weighted_percentile (vis.py:22-30): the weighted percentiles `ps` (1 to 4 numbers in [0, 100]) of the values x with
   weights w, both flattened, as a float32 device tensor [len(ps)]; nothing is read back.  The order comes from a stable
@@ -1730,6 +1763,46 @@ def tsdf_integrate(tsdf, weight, color, origin, spacing, trunc, proj, depth, acc
   a.proj, a.depth, a.acc, a.rgb = proj.data_ptr(), depth.data_ptr(), _ptr(acc), _ptr(rgb)
   a.tsdf, a.weight, a.color = tsdf.data_ptr(), weight.data_ptr(), _ptr(color)
   L.check(lib().mnr_tsdf_integrate(C.byref(a), _stream()))
+
+
+def tsdf_integrate_cam(tsdf, weight, color, origin, spacing, trunc, cameras, depth, acc=None, rgb=None, acc_threshold=0.5):
+  """`tsdf_integrate` for any camera model (mnr_tsdf_integrate_cam; include/mnerf.h): instead of proj, cameras [F,_lib.CAM_REC]
+  float32 holds one record of mesh.camera_record a frame (a host array or any tensor: it is checked on the host and copied to
+  the volumes' device), all of one model and of the images' height and width; depth [F,H,W] holds s, the distance rendered
+  along the camera's own rays (the depth of mesh.render_mesh(method='raycast')).  Everything else is tsdf_integrate's."""
+  name = 'tsdf_integrate_cam'
+  for t, label in ((tsdf, 'tsdf'), (weight, 'weight'), (depth, 'depth')):
+    _chk(t, f32, label)
+  _chk(color, f32, 'color', allow_none=True)
+  _chk(acc, f32, 'acc', allow_none=True)
+  _chk(rgb, f32, 'rgb', allow_none=True)
+  if tsdf.dim() != 3 or weight.shape != tsdf.shape or (color is not None and tuple(color.shape) != tuple(tsdf.shape) + (3,)):
+    raise ValueError(f'{name}: tsdf and weight must be [nx,ny,nz] and color [nx,ny,nz,3]')
+  if (color is None) != (rgb is None):
+    raise ValueError(f'{name}: rgb and color are both given or both None')
+  if depth.dim() != 3:
+    raise ValueError(f'{name}: depth must be [F,H,W], is {tuple(depth.shape)}')
+  if (acc is not None and acc.shape != depth.shape) or (rgb is not None and tuple(rgb.shape) != tuple(depth.shape) + (3,)):
+    raise ValueError(f'{name}: acc must be [F,H,W] and rgb [F,H,W,3] for depth {tuple(depth.shape)}')
+  F, H, W = (int(v) for v in depth.shape)
+  rec, model = camera_record_host(name, cameras, rows=F)
+  if F and not ((rec[:, 26] == H).all() and (rec[:, 27] == W).all()):
+    raise ValueError(f'{name}: the records were built for images of another size than depth {tuple(depth.shape)}')
+  spacing, trunc = float(spacing), float(trunc)
+  if not (spacing > 0. and math.isfinite(spacing)) or not (trunc > 0. and math.isfinite(trunc)):
+    raise ValueError(f'{name}: spacing and trunc must be positive and finite, are {spacing} and {trunc}')
+  origin = finite3(name, 'origin', origin)
+  if F == 0:                                                # (an empty stack has no pointers to hand over)
+    return
+  rec_dev = torch.from_numpy(rec).to(tsdf.device)
+  a = L.TsdfCamArgs()
+  a.nx, a.ny, a.nz = (int(v) for v in tsdf.shape)
+  a.origin[0], a.origin[1], a.origin[2] = origin
+  a.spacing, a.trunc, a.acc_threshold = spacing, trunc, float(acc_threshold)
+  a.F, a.H, a.W, a.model = F, H, W, model
+  a.cameras, a.depth, a.acc, a.rgb = rec_dev.data_ptr(), depth.data_ptr(), _ptr(acc), _ptr(rgb)
+  a.tsdf, a.weight, a.color = tsdf.data_ptr(), weight.data_ptr(), _ptr(color)
+  L.check(lib().mnr_tsdf_integrate_cam(C.byref(a), _stream()))
 
 
 # ----------------------------------------------------------------------------- mesh clean-up (csrc/meshclean.hip)
